@@ -1,14 +1,21 @@
 """bench.py — VAMP iterations/s + HBM GB/s on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config auto|c2|c3full|c3|c3big|c4|c4full|c5]
-                    [--no-cpu-baseline] [--no-read-ceiling] [--no-timing | --timing-period P]
+                    [--dump-outputs DIR] [--no-timing | --timing-period P]
+                    [--full [--no-cpu-baseline] [--no-read-ceiling] [--no-headline]]
                     [--rehearse P]   (the n > 1 flow with P loopback rank threads on one GPU)
+
+A plain run sets up, runs W untimed and K timed steps, writes the outputs of
+the last step if --dump-outputs is given and prints the line.  --full adds the
+legs that take runs of their own: the CPU baselines, the same-run HBM read
+ceiling and, at n > 1, rank 0's 1-GPU bases and the configs[2] headline phase.
 
 The line's `roofline` is the dominant kernel's algorithmic bytes per launch
 over its HIP-event launch time, against the 8 TB/s spec (`frac`), against the
-pool's measured read ceiling (`frac_of_read_ceiling`, profiles/) and, at
-n = 1, against a pure read stream of the same resident matrix measured by this
-process right after the timed region (`frac_of_read_ceiling_same_run`).
+pool's measured read ceiling (`frac_of_read_ceiling`, profiles/) and, with
+--full at n = 1, against a pure read stream of the same resident matrix
+measured by this process right after the timed region
+(`frac_of_read_ceiling_same_run`).
 
 A "step" is one VAMP iteration (src/vamp.cpp:148-428) of the linear model
 (or src/vamp_probit.cpp:68-463 of the probit model for c4) over the whole
@@ -19,9 +26,9 @@ are untimed.
 Workloads (synthetic, generated on the device):
   auto (default)  c2 at every n: n = 1 is BASELINE configs[1]; n > 1 is its
           weak-scaling form c2-weak (50,000 markers per GPU), so the driver's
-          1 -> 8 curve compares one workload family.  At n > 1 the same line
-          also carries `headline_c3full`, configs[2] itself (N=100,000 x
-          Mt=500,000, the metric's own problem) run in the same job, and the
+          1 -> 8 curve compares one workload family.  At n > 1 with --full
+          the same line also carries `headline_c3full`, configs[2] itself
+          (N=100,000 x Mt=500,000, the metric's own problem) run in the same job, and the
           1-GPU bases both are read against, measured in the same job on
           rank 0's GPU before the n-rank phases (`one_gpu`).
   c2      N=10,000 x Mt=50,000 i.i.d. Gaussian design (BASELINE configs[1]);
@@ -85,12 +92,20 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="auto", choices=["auto", "c2", "c3full", "c3", "c3big", "c4", "c4full", "c5"])
     ap.add_argument("--seed", type=int, default=20250711)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: the CPU baselines (the oracle port and the "
+                         "reference's own operators), the same-run HBM read ceiling and, at n > 1, rank 0's 1-GPU "
+                         "bases and the configs[2] headline phase")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64): the "
+                         "estimate a caller receives and the last iteration's parameter and metric rows (c5: the "
+                         "p-values); the inputs depend on --seed and --config alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-budget", type=float, default=45.0, help="seconds of host time for the CPU baseline")
     ap.add_argument("--no-timing", action="store_true", help="skip the HIP-event kernel timing")
     ap.add_argument("--no-read-ceiling", action="store_true",
-                    help="skip the same-run HBM read ceiling (a pure read stream of the resident matrix, after the "
-                         "timed region, n = 1)")
+                    help="with --full: skip the same-run HBM read ceiling (a pure read stream of the resident matrix, "
+                         "after the timed region, n = 1)")
     ap.add_argument("--timing-period", type=int, default=4,
                     help="time one A/A^T launch in this many of each (kernel, K) with HIP events (positions chosen "
                          "by a hash of the launch index; every launch timed costs 1-2.6 %% of a C2 iteration, "
@@ -109,10 +124,12 @@ def parse_args(argv=None):
                     help="the whole run's time limit: past it every rank stops and rank 0 prints a JSON line with "
                          "\"error\" and each rank's last stage (keep it under the caller's own limit)")
     ap.add_argument("--no-headline", action="store_true",
-                    help="n > 1 with --config auto: skip the configs[2] (c3full) phase and its 1-GPU basis")
+                    help="with --full at n > 1 and --config auto: skip the configs[2] (c3full) phase and its "
+                         "1-GPU basis")
     ap.add_argument("--rehearse", type=int, default=0, metavar="P",
                     help="rehearsal of the n > 1 flow on ONE GPU: P loopback ranks as threads of this process on "
-                         "GPU 0 (bases, main phase, headline phase, line assembly), every workload's markers "
+                         "GPU 0 (main phase, line assembly; with --full the bases and headline phase), every "
+                         "workload's markers "
                          "scaled by --rehearse-scale; the rate is not a multi-GPU number")
     ap.add_argument("--rehearse-scale", type=float, default=0.05)
     return ap.parse_args(argv)
@@ -359,6 +376,29 @@ def same_run_ceiling(args, d, roof, n: int):
     roof["read_ceiling_same_run"] = {"GBs": round(c["GBs"], 1), "us_med": round(c["us_med"], 2),
                                      "bytes": int(c["bytes"]), "variant": c["variant"]}
     roof["frac_of_read_ceiling_same_run"] = round(roof["achieved"] / c["GBs"], 4)
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir: str, arrays: dict, seed: int) -> dict:
+    """--dump-outputs: every array as out_dir/<name>.npy in float64, at most
+    64 MB in all.  An array over its share is cut to a fixed sample of its
+    flattened entries (indices drawn from `seed` and the size alone, sorted),
+    so two builds write the same entries.  Returns {name: entries written}."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // (8 * max(len(arrays), 1))
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        written[name] = int(a.size)
+    return written
 
 
 def roofline(ks, kname: str, workload: str, period: int) -> dict:
@@ -824,7 +864,7 @@ def vamp_window(args, R, w: dict, wd: Watchdog, steps: int, warmup: int, tag: st
                "M": d.M, "nranks": d.nranks, "steps": steps, "warmup": warmup, "model": model, "beta": beta,
                "opts": opts, "barrier": barrier}
         res["rank_times"] = per_rank_times(R, st, el)
-        v.end()
+        res["x1_final"] = v.end()  # what vamp::infere returns after the last timed iteration (this rank's slice)
         if keep:
             res["d"] = d
             d = None
@@ -833,6 +873,24 @@ def vamp_window(args, R, w: dict, wd: Watchdog, steps: int, warmup: int, tag: st
         if d is not None:
             wd.stage(f"{tag}: close")
             d.close()
+
+
+def dump_vamp_outputs(args, R, res: dict):
+    """--dump-outputs of a VAMP window (COLLECTIVE): the estimate vamp::infere
+    returns after the last timed iteration (every rank's slice, in rank order)
+    and that iteration's rows of the parameter, metric and solver-step
+    histories (probit: its prior row too).  Rank 0 writes."""
+    import numpy as np
+
+    parts = R.gather(res["x1_final"])
+    if R.rank != 0:
+        return None
+    s = res["summ"]
+    arrays = {"x1_hat": np.concatenate(parts), "params": s["params"][-1], "metrics": s["metrics"][-1],
+              "solver_steps": [s["cg_iters"][-1], s["ons_iters"][-1]]}
+    if "prior" in s:
+        arrays["prior"] = s["prior"][-1]
+    return dump_outputs(args.dump_outputs, arrays, args.seed)
 
 
 def dominant_roofline(args, res: dict, w: dict, kernel_name) -> dict:
@@ -917,15 +975,19 @@ def run_linear(args, R: Ranks, wd: Watchdog, w: dict, t_start: float) -> dict:
     n = R.world
     strong = w.get("scaling") == "strong"
     auto_multi = args.config == "auto" and n > 1
-    headline = auto_multi and not args.no_headline
-    bases = one_gpu_bases(args, R, wd, w, headline or (strong and w["workload"] == "c3full")) if n > 1 else {}
+    headline = auto_multi and args.full and not args.no_headline
+    cpu_legs = R.rank == 0 and n == 1 and args.full and not args.no_cpu_baseline
+    bases = (one_gpu_bases(args, R, wd, w, headline or (strong and w["workload"] == "c3full"))
+             if (n > 1 and args.full) else {})
 
     res = vamp_window(args, R, w, wd, args.steps, args.warmup, "main", keep=True)
     d, st, el, model = res["d"], res["st"], res["el"], res["model"]
     try:
+        dumped = dump_vamp_outputs(args, R, res) if args.dump_outputs else None
         roof = dominant_roofline(args, res, w, d.kernel_name)
-        same_run_ceiling(args, d, roof, n)
-        y = d.get_phen() if (R.rank == 0 and n == 1 and not args.no_cpu_baseline) else None
+        if args.full:
+            same_run_ceiling(args, d, roof, n)
+        y = d.get_phen() if cpu_legs else None
         with_writes = (write_rate(args, d, R, res["opts"], res["beta"], res["barrier"], el) if args.write else None)
     finally:
         wd.stage("main: close")
@@ -968,6 +1030,9 @@ def run_linear(args, R: Ranks, wd: Watchdog, w: dict, t_start: float) -> dict:
                                       "writes); see with_writes" if args.write else
                                       "not written in the timed window (BASELINE.md: the metric excludes output-file "
                                       "writes; bench.py --write times them)")
+    if dumped:
+        line["outputs"] = {"dir": args.dump_outputs, "entries": dumped, "dtype": "float64",
+                           "what": "the last timed iteration's results, one .npy file per name"}
     if with_writes:
         ws = with_writes.pop("elapsed_s")
         with_writes["value"] = round(args.steps / ws if strong else n * args.steps / ws, 4)
@@ -976,7 +1041,7 @@ def run_linear(args, R: Ranks, wd: Watchdog, w: dict, t_start: float) -> dict:
         line["scaling_basis"] = (
             "read against the n = 1 line of the same workload family: `python bench.py --gpus 1` (c2, configs[1]: "
             "N = 10,000 x 50,000, the same per-GPU shard as c2-weak)" if w["workload"] == "c2-weak" else
-            "one_gpu.c3big (measured in this job; configs[2] does not fit one GPU)" if strong else
+            "one_gpu.c3big (measured in this job with --full; configs[2] does not fit one GPU)" if strong else
             f"the n = 1 line of --config {args.config}")
         one = {}
         if "same_problem" in bases:
@@ -999,7 +1064,7 @@ def run_linear(args, R: Ranks, wd: Watchdog, w: dict, t_start: float) -> dict:
     if model == "bin_class":
         line["parity_note"] = ("probit: x1_hat/r1 parity bar is max(1e-10, k x the oracle's own rank-count spread), "
                                "integers exact (DESIGN.md §3)")
-    if R.rank == 0 and n == 1 and not args.no_cpu_baseline:
+    if cpu_legs:
         wd.stage("cpu baseline")
         if w["workload"] == "c3big":
             # the oracle's leg would generate the whole 240 GB matrix on the host
@@ -1104,11 +1169,17 @@ def bench_assoc(args, R: Ranks, wd: Watchdog, w: dict, t_start):
     barrier()
     el = R.max(time.perf_counter() - t0)
     st = d.stats()
+    dumped = None
+    if args.dump_outputs:  # the last test's p-values, every rank's slice in rank order (COLLECTIVE)
+        parts = R.gather(p_t[: d.M].cpu().numpy())
+        if R.rank == 0:
+            dumped = dump_outputs(args.dump_outputs, {"pvals": np.concatenate(parts)}, args.seed)
     roof = None
     if st.loo.timed:
         roof = roofline(st.loo, d.kernel_name(2, 1, 0), w["workload"], args.timing_period)
         roof["ax_avg_launch_us"] = round(st.ax.ms_timed / max(st.ax.timed, 1) * 1e3, 2)
-        same_run_ceiling(args, d, roof, R.world)
+        if args.full:
+            same_run_ceiling(args, d, roof, R.world)
     line = {
         "metric": "LOO association test: markers tested/s (+ achieved HBM GB/s of the per-marker pass)",
         "value": round(Mt * args.steps / el, 1),
@@ -1123,7 +1194,10 @@ def bench_assoc(args, R: Ranks, wd: Watchdog, w: dict, t_start):
         "setup_s": round(t_setup, 2),
         "cpu_baseline": None,
     }
-    if R.rank == 0 and R.world == 1 and not args.no_cpu_baseline:
+    if dumped:
+        line["outputs"] = {"dir": args.dump_outputs, "entries": dumped, "dtype": "float64",
+                           "what": "the last timed test's results, one .npy file per name"}
+    if R.rank == 0 and R.world == 1 and args.full and not args.no_cpu_baseline:
         wd.stage("cpu baseline")
         try:
             line["cpu_baseline"] = cpu_baseline_assoc(d, w, est, args.seed)
@@ -1182,8 +1256,8 @@ class ThreadRanks:
 
 
 def rehearse(args) -> int:
-    """--rehearse P: the whole n > 1 flow of `bench.py --gpus P` (rank 0's
-    1-GPU bases, the main phase, the configs[2] headline phase, the line) with
+    """--rehearse P: the n > 1 flow of `bench.py --gpus P` (the main phase and
+    the line; with --full rank 0's 1-GPU bases and the configs[2] headline phase too) with
     P loopback ranks as threads on GPU 0 and every workload's markers scaled
     by --rehearse-scale, so that the driver's first multi-GPU run is not the
     first time this code path runs on the device.  Prints rank 0's line with

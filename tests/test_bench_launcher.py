@@ -195,7 +195,7 @@ def test_multi_rank_line_assembly(monkeypatch):
 
     calls = []
     monkeypatch.setattr(bench, "vamp_window", _fake_window(calls))
-    args = bench.parse_args(["--gpus", "4", "--steps", "20", "--warmup", "5"])
+    args = bench.parse_args(["--gpus", "4", "--steps", "20", "--warmup", "5", "--full"])
     line = bench.run_linear(args, _Ranks(4), _Wd(), workload("auto", 4), 0.0)
     json.dumps(line)
     assert [c[0] for c in calls] == ["basis same-problem", "basis c3big", "main", "headline"]
@@ -213,7 +213,7 @@ def test_multi_rank_line_assembly(monkeypatch):
 
     # explicit c3full: the strong line itself carries the measured equivalent
     calls.clear()
-    args = bench.parse_args(["--gpus", "2", "--steps", "20", "--warmup", "5", "--config", "c3full"])
+    args = bench.parse_args(["--gpus", "2", "--steps", "20", "--warmup", "5", "--config", "c3full", "--full"])
     line = bench.run_linear(args, _Ranks(2), _Wd(), workload("c3full", 2), 0.0)
     assert [c[0] for c in calls] == ["basis c3big", "main"]
     assert line["scaling"] == "strong" and line["one_gpu_equivalent"]["measured_in_this_job"]
@@ -271,7 +271,7 @@ def _stub_library(monkeypatch):
 
     class Vamp:
         def __init__(self, d, opts, true_signal=None):
-            self.n = 0
+            self.n, self.M = 0, d.M
 
         def begin(self):
             pass
@@ -284,10 +284,12 @@ def _stub_library(monkeypatch):
             return 37.7 * self.n, 8.3 * self.n
 
         def summary(self):
-            return {"cg_iters": [7] * self.n, "ons_iters": [8] * self.n}
+            return {"cg_iters": [7] * self.n, "ons_iters": [8] * self.n,
+                    "params": [[0.5 * k, 1.0, 2.0, 3.0, 4.0] for k in range(self.n)],
+                    "metrics": [[0.25 * k] * 6 for k in range(self.n)]}
 
         def end(self):
-            pass
+            return [float(self.n)] * self.M
 
     monkeypatch.setattr(va, "Data", Data)
     monkeypatch.setattr(va, "Vamp", Vamp)
@@ -303,7 +305,7 @@ def test_vamp_window_and_bases_with_a_stub_library(monkeypatch):
     from vampomi_amd.workloads import workload
 
     _stub_library(monkeypatch)
-    args = bench.parse_args(["--gpus", "2", "--steps", "3", "--warmup", "1"])
+    args = bench.parse_args(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full"])
     out = bench.one_gpu_bases(args, _Ranks(2), _Wd(), workload("auto", 2), True)
     assert set(out) == {"same_problem", "c3big"}, out
     assert "error" not in out["same_problem"] and "error" not in out["c3big"], out
@@ -323,7 +325,7 @@ def test_rehearsal_flow_with_a_stub_library(monkeypatch, capsys):
     _stub_library(monkeypatch)
     monkeypatch.setenv("TMPDIR", os.environ.get("TMPDIR", "/tmp"))
     args = bench.parse_args(["--rehearse", "3", "--rehearse-scale", "0.1", "--steps", "2", "--warmup", "1",
-                             "--deadline-s", "120"])
+                             "--deadline-s", "120", "--full"])
     try:
         rc = bench.rehearse(args)
     finally:
@@ -366,3 +368,74 @@ def test_same_run_ceiling_fields():
     bench.same_run_ceiling(NS(no_read_ceiling=False), Bad(), r, 1)
     assert "error" in r["read_ceiling_same_run"] and "frac_of_read_ceiling_same_run" not in r
     bench.same_run_ceiling(NS(no_read_ceiling=False), D(), None, 1)  # no roofline: nothing to do
+
+
+def test_plain_run_leaves_the_other_legs_to_full(monkeypatch):
+    """Without --full the line comes from the warmup and the timed steps alone:
+    no CPU baseline, no same-run read ceiling, and at n > 1 neither the 1-GPU
+    bases nor the configs[2] phase; --full runs every one of them."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from vampomi_amd.workloads import workload
+
+    _stub_library(monkeypatch)
+    legs = []
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **k: legs.append("port") or {"value": 0.4, "kind": "port"})
+    monkeypatch.setattr(bench, "cpu_reference_ops", lambda *a, **k: legs.append("ref") or {"value": 0.1})
+    ceiling = bench.same_run_ceiling
+    monkeypatch.setattr(bench, "same_run_ceiling", lambda *a: legs.append("ceiling") or ceiling(*a))
+    plain = ["--gpus", "1", "--steps", "3", "--warmup", "1"]
+    line = bench.run_linear(bench.parse_args(plain), _Ranks(1), _Wd(), workload("auto", 1), 0.0)
+    assert legs == [] and line["cpu_baseline"] is None and "cpu_reference_ops" not in line
+    assert "read_ceiling_same_run" not in line["roofline"] and line["roofline"]["achieved"] > 0
+    assert line["steps"] == 3 and line["ms_per_step"] >= 0 and line["dtype"] == "f64" and line["higher_is_better"]
+    assert line["unit"] == "iterations/s" and line["metric"].startswith("VAMP iterations/s")
+    full = bench.run_linear(bench.parse_args(plain + ["--full"]), _Ranks(1), _Wd(), workload("auto", 1), 0.0)
+    assert legs == ["ceiling", "port", "ref"] and full["cpu_baseline"]["kind"] == "port"
+    assert full["roofline"]["read_ceiling_same_run"]["variant"] == "stub"
+    assert {k: full[k] for k in ("metric", "unit", "dtype", "higher_is_better")} == \
+        {k: line[k] for k in ("metric", "unit", "dtype", "higher_is_better")}
+
+    calls = []
+    monkeypatch.setattr(bench, "vamp_window", _fake_window(calls))
+    args = bench.parse_args(["--gpus", "4", "--steps", "20", "--warmup", "5"])
+    line = bench.run_linear(args, _Ranks(4), _Wd(), workload("auto", 4), 0.0)
+    assert [c[0] for c in calls] == ["main"] and "headline_c3full" not in line and "one_gpu" not in line
+    assert line["value"] == round(4 * 20 / ((8.3 * 0.6 + 0.3) * 20e-3), 4)
+
+
+def test_dump_outputs(monkeypatch, tmp_path):
+    """--dump-outputs DIR: the last timed step's results as float64 .npy files,
+    the same from run to run; every timed step runs (--steps sets their number);
+    an array over its share of the 64 MB is cut to a fixed seeded sample."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from vampomi_amd.workloads import workload
+
+    _stub_library(monkeypatch)
+    for sub, steps in (("a", 3), ("b", 3), ("c", 5)):
+        args = bench.parse_args(["--gpus", "1", "--steps", str(steps), "--warmup", "2", "--dump-outputs",
+                                 str(tmp_path / sub)])
+        line = bench.run_linear(args, _Ranks(1), _Wd(), workload("auto", 1), 0.0)
+        assert line["outputs"]["entries"]["x1_hat"] == 50000 and line["steps"] == steps
+    got = {sub: {f[:-4]: np.load(tmp_path / sub / f) for f in sorted(os.listdir(tmp_path / sub))} for sub in "abc"}
+    assert all(f.endswith(".npy") for f in os.listdir(tmp_path / "a"))
+    assert set(got["a"]) == {"x1_hat", "params", "metrics", "solver_steps"}
+    for f, a in got["a"].items():
+        assert a.dtype == np.float64 and np.array_equal(a, got["b"][f])
+    assert got["a"]["x1_hat"].shape == (50000,) and np.all(got["a"]["x1_hat"] == 5.0)  # the stub counts its steps
+    assert np.all(got["c"]["x1_hat"] == 7.0) and got["c"]["params"][0] == 0.5 * 6  # the last iteration's row
+    assert got["a"]["solver_steps"].tolist() == [7.0, 8.0]
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * 8 * 100)
+    big, small = np.arange(1000.0), np.arange(60.0)
+    for sub in ("s1", "s2"):
+        n = bench.dump_outputs(str(tmp_path / sub), {"big": big, "small": small}, 7)
+        assert n == {"big": 100, "small": 60}
+    s1, s2 = np.load(tmp_path / "s1" / "big.npy"), np.load(tmp_path / "s2" / "big.npy")
+    assert s1.shape == (100,) and np.array_equal(s1, s2) and np.all(np.diff(s1) > 0)
+    assert np.array_equal(np.load(tmp_path / "s1" / "small.npy"), small)
+    total = sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1"))
+    assert total <= 2 * 8 * 100 + 2 * 128  # the .npy headers

@@ -106,28 +106,46 @@ def test_update_prior_entry_point(em, lv, merge):
 def test_device_memory_plan_matches_the_allocations(tmp_path):
     """vampomi_dev_mem_plan (the CPU-side budget tests/test_op_plan.py checks
     for c3full at n = 2, 4, 8) against the device memory a C2-sized context
-    really takes during a run with the team operator and the writer on."""
+    really takes during a run with the team operator and the writer on.
+
+    The readings are the device's free memory, which every process on the GPU
+    moves (a child of an earlier test still exiting, the first context's own
+    runtime allocations): a measurement counts only if the free memory is back
+    at its starting value once the context is closed, and is taken again
+    otherwise, three times at the most.  The bound itself is unchanged."""
     import ctypes as C
 
     import torch
 
     N, Mt = 10000, 50000
     torch.cuda.init()
-    free0, _ = torch.cuda.mem_get_info()
-    with va.Data(N, Mt) as d:
-        d.generate(3, va.GEN_GAUSS)
-        beta = d.simulate_phen(4)
-        v = va.Vamp(d, va.VampOptions(max_iter=2, stop_criteria_thr=0.0, out_dir=str(tmp_path), out_name="m"),
-                    true_signal=beta)
-        v.begin()
-        v.step()
-        free1, _ = torch.cuda.mem_get_info()
-        v.step()
-        v.end()
-        cus = torch.cuda.get_device_properties(0).multi_processor_count
+
+    def measure(k):
+        free0, _ = torch.cuda.mem_get_info()
+        with va.Data(N, Mt) as d:
+            d.generate(3, va.GEN_GAUSS)
+            beta = d.simulate_phen(4)
+            out = tmp_path / f"try{k}"
+            out.mkdir()
+            v = va.Vamp(d, va.VampOptions(max_iter=2, stop_criteria_thr=0.0, out_dir=str(out), out_name="m"),
+                        true_signal=beta)
+            v.begin()
+            v.step()
+            free1, _ = torch.cuda.mem_get_info()
+            v.step()
+            v.end()
+        free2, _ = torch.cuda.mem_get_info()
+        return free0 - free1, free2 - free0
+
+    for k in range(3):
+        used, drift = measure(k)
+        if abs(drift) <= 16 * 2**20:
+            break
+    else:
+        pytest.fail(f"the device's free memory moved by {drift / 2**20:.0f} MiB around each of 3 measurements")
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
     b = C.c_int64()
     assert va.load().vampomi_dev_mem_plan(N, Mt, 1, 0, cus, 0, 1, C.byref(b)) == 0
-    used = free0 - free1
     assert abs(used - b.value) <= 256 * 2**20 + 0.02 * b.value, (used / 2**20, b.value / 2**20)
 
 

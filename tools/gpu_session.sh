@@ -8,7 +8,7 @@
 #   suite        the GPU test suite (durations of the slowest tests)
 #   fullshard    the whole-shard oracle tests alone (C3, C4, C5)
 #   tests        the GPU tests named in $TESTS (pytest arguments; $TESTK: a -k expression)
-#   rehearse     bench.py's n > 1 flow with 8 loopback rank threads on this GPU
+#   rehearse     bench.py --full's n > 1 flow with 8 loopback rank threads on this GPU
 #   bitwise      12 VAMP iterations (linear and probit; N x Mt = $BWN x $BWM, default 10000 x 20000) on this build and on
 #                $OLD (default build_ab/, make -C vampomi_amd/csrc OBJDIR=../../build_ab/obj LIBDIR=../../build_ab/lib BINDIR=../../build_ab/bin at the base commit), compared bit for bit
 #   ab           C2 lines alternating this build and $OLD, $ROUNDS rounds
@@ -25,10 +25,10 @@
 #   rccl         the 1-rank RCCL path against the direct one (rates, timing on/off, traces compared)
 #   ceiling      the HBM read ceiling of this box (tools/hbm_ceiling, 4 GB and 50 GB buffers)
 #   ablation     the C2 operator's components removed one at a time (tools/op_ablation.py, build_dbg/: TM_DBG=1)
-#   benchc2      the default C2 line, both CPU legs
+#   benchc2      the default C2 line with --full (both CPU legs, the same-run read ceiling)
 #   c4           the probit shard's line and its per-iteration kernel trace
 #   bases        rank 0's 1-GPU bases (tools/one_gpu_bases.py)
-#   final        smoke, the default C2 line (both CPU legs), its kernel stats
+#   final        smoke, the default C2 line (--full: both CPU legs), its kernel stats
 #                and PMC traffic; the same for C3; C4 and C5 lines
 set -u
 cd "${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
@@ -72,7 +72,7 @@ for s in "$@"; do
         [ -f "$VAMPOMI_PROBIT_RATIOS" ] && python tools/probit_ratios.py "$VAMPOMI_PROBIT_RATIOS" | tee "$OUT/probit_k.txt"
         unset VAMPOMI_PROBIT_RATIOS ;;
     rehearse)
-        step rehearse 400 python bench.py --rehearse 8 --steps 3 --warmup 1 --deadline-s 380 ;;
+        step rehearse 400 python bench.py --rehearse 8 --full --steps 3 --warmup 1 --deadline-s 380 ;;
     bitwise)
         for m in linear bin_class; do
             step bw_new_$m 200 python tools/lib_bitwise.py run "$OUT/new_$m.npz" "${BWN:-10000}" "${BWM:-20000}" 12 $m
@@ -157,8 +157,8 @@ for s in "$@"; do
         step ablation 400 env VAMPOMI_LIB="$PWD/build_dbg/lib/libvampomi.so" python tools/op_ablation.py 10000 50000 40 3 ;;
     ablibs)      # the C2 operator with a component removed at compile time (TM_ABL builds), against production
         step ablibs 600 bash tools/op_ablation_libs.sh 3 ;;
-    benchc2)     # the default C2 line with both CPU legs
-        step bench_c2 400 python bench.py --steps 20 --warmup 5 ;;
+    benchc2)     # the default C2 line with --full: both CPU legs, the same-run read ceiling
+        step bench_c2 400 python bench.py --full --steps 20 --warmup 5 ;;
     c4)          # the probit shard: its line, and a kernel trace of 10 iterations (A passes against the rest)
         step bench_c4 400 python bench.py --config c4 --steps 6 --warmup 2 --no-cpu-baseline
         step trace_c4 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_c4" -o run --output-format csv -- \
@@ -171,14 +171,14 @@ for s in "$@"; do
         step bases 200 python tools/one_gpu_bases.py ;;
     final)
         step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-        step bench_c2 400 python bench.py --steps 20 --warmup 5
+        step bench_c2 400 python bench.py --full --steps 20 --warmup 5
         prof c2 20
         step pmc_c2 300 bash tools/pmc.sh c2
-        step bench_c3 400 python bench.py --config c3 --steps 10 --warmup 2
+        step bench_c3 400 python bench.py --config c3 --full --steps 10 --warmup 2
         prof c3 6
         step pmc_c3 300 bash tools/pmc.sh c3
-        step bench_c4 400 python bench.py --config c4 --steps 6 --warmup 2   # iterations 3-8: inside test_c4_full_shard_vs_oracle
-        step bench_c5 300 python bench.py --config c5 --steps 5 --warmup 1 ;;
+        step bench_c4 400 python bench.py --config c4 --full --steps 6 --warmup 2   # iterations 3-8: inside test_c4_full_shard_vs_oracle
+        step bench_c5 300 python bench.py --config c5 --full --steps 5 --warmup 1 ;;
     *)
         echo "unknown step $s"; exit 2 ;;
     esac
