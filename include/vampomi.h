@@ -330,8 +330,15 @@ vampomi_status vampomi_reset_stats(vampomi_ctx* ctx);
  * vampomi_vamp_begin (or vampomi_infere), where the ranks agree on them: the
  * one-pass operator runs only if every rank has a plan for it, the head start
  * and the host-free tail only if every rank has them on (each changes the
- * job's collective sequence). */
+ * job's collective sequence).
+ * which = 7: the pre-step of the linear model on one rank (an operator slot
+ * whose system has stopped forms the next Onsager solve's first CG step,
+ * pcg.cpp): 0 off, 1 on at any size, 2 auto (default: on where the head start
+ * runs and the X shard is at least 256 MiB; VAMPOMI_PRESTEP sets the same
+ * values at vampomi_open).  Takes effect at the next iteration's solve. */
 vampomi_status vampomi_dev_set_variant(vampomi_ctx* ctx, int which, int variant);
+/* pre-steps made and used since vampomi_vamp_begin (which = 7 above) */
+vampomi_status vampomi_dev_prestep_counts(const vampomi_ctx* ctx, int64_t* made, int64_t* used);
 /* average device time (HIP events) of `reps` back-to-back launches, K RHS */
 vampomi_status vampomi_dev_time_pass(vampomi_ctx* ctx, int which, int K, int reps, double* avg_ms);
 /* The HBM read ceiling of this device for this shard: a pure read stream of

@@ -294,6 +294,12 @@ class Data:
         """Development hook: this context's kernel variant for pass ``which``."""
         check(self._lib.vampomi_dev_set_variant(self.ctx, which, variant))
 
+    def prestep_counts(self) -> tuple:
+        """(made, used): the pre-steps of the linear model's solves since the run began."""
+        made, used = C.c_int64(), C.c_int64()
+        check(self._lib.vampomi_dev_prestep_counts(self.ctx, C.byref(made), C.byref(used)))
+        return made.value, used.value
+
     def all_ok(self, local_ok: bool) -> bool:
         """COLLECTIVE: True iff local_ok on every rank."""
         out = C.c_int()

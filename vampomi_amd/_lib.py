@@ -137,6 +137,7 @@ SIGNATURES = {
     "vampomi_get_stats": (C.c_int, [_P, C.POINTER(Stats)]),
     "vampomi_reset_stats": (C.c_int, [_P]),
     "vampomi_dev_set_variant": (C.c_int, [_P, C.c_int, C.c_int]),
+    "vampomi_dev_prestep_counts": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "vampomi_dev_time_pass": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "vampomi_dev_read_ceiling": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                            C.POINTER(C.c_int)]),

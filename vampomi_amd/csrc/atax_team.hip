@@ -237,6 +237,39 @@ __device__ __forceinline__ Tp* tm_chk(Tp* p, const void* lo, const void* hi, uns
     return p;
 }
 
+// the systems' pointers and scalars per slot: OpArgs', or the alternate
+// system's in slot alt (OpAlt: diag = tau = 1, gam2 = 0; its raw product t
+// equals its d but for the sign of a zero, and d's store is the later one)
+template <int K>
+struct TmSlots {
+    const double* ar[K];
+    const double* p[K];
+    double* d[K];
+    double* sraw[K];
+    double diag[K], tau[K], gam2[K];
+};
+template <int K>
+__device__ __forceinline__ TmSlots<K> tm_slots(const OpArgs& a, int alt) {
+    TmSlots<K> s;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        // one indexed read of the launch's slot table per value (the index is
+        // opaque, so that the compiler does not load both candidates and hold
+        // them in scalar registers until it selects)
+        int idx = k == alt ? kOpMaxK : k;
+        asm volatile("" : "+s"(idx));
+        const OpAlt::Slot& t = a.alt.tab[idx];
+        s.ar[k] = t.ar;
+        s.p[k] = t.p;
+        s.d[k] = t.d;
+        s.sraw[k] = t.sraw;
+        s.diag[k] = t.diag;
+        s.tau[k] = t.tau;
+        s.gam2[k] = t.gam2;
+    }
+    return s;
+}
+
 template <int K, int S, int F, int L, int P, bool COMM, int E, bool FMA, int KP>
 __device__ __forceinline__ void atax_team_body(const double* __restrict__ X, int64_t ld, int64_t N, int64_t M,
                                                const double* __restrict__ mave, const double* __restrict__ msig,
@@ -272,6 +305,17 @@ __device__ __forceinline__ void atax_team_body(const double* __restrict__ X, int
     }
     const double* beta = a.fold.on ? s_beta : a.beta;
     static_assert(K + KP <= kMaxRhs, "partial slots per team");
+    // The pre-step (kernels.h OpAlt): the lowest slot whose system has stopped,
+    // if this solve has made none yet, runs on the alternate system instead.
+    // Uniform over the grid: every wave evaluates it from the same scalar
+    // loads (the state and the done word; nothing writes either while this
+    // launch runs).  Each half of the kernel then takes its per-slot pointers
+    // and scalars (tm_slots) where it starts
+    int fuse = a.fuse, alt = -1;
+    if constexpr (KP == 0) {
+        if (a.alt.cs && !a.fold.on) alt = cg_pre_slot(a.alt.cs->active, K, *a.alt.done == a.alt.token);
+        if (alt >= 0) fuse &= ~(1 << alt);
+    }
 #if TM_TS
     const unsigned long long ts0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -335,6 +379,7 @@ __device__ __forceinline__ void atax_team_body(const double* __restrict__ X, int
         // and the compiler's own loads only add younger operations: the wait
         // stays sufficient).  Every poll register passes through such a wait
         // before it is read or reused (the compiler sees the wait as its writer).
+        const TmSlots<K> sl = tm_slots<K>(a, alt);
         const int nq = K * T;
         // granules of step m at xg + m * nq2: the team's m-th column
         unsigned long long* xg = a.xg + (int64_t)team * nmax * nq * 2;
@@ -351,14 +396,14 @@ __device__ __forceinline__ void atax_team_body(const double* __restrict__ X, int
         const double* scp = msig;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            if (lane == 1 + k) scp = a.p.p[k];
-            if (lane == 1 + K + k && ((a.fuse >> k) & 1)) scp = a.z.p[k];
+            if (lane == 1 + k) scp = sl.p[k];
+            if (lane == 1 + K + k && ((fuse >> k) & 1)) scp = a.z.p[k];
         }
         scp += mb;  // column m (relative) is scp[m * cs]
         double bk[K], dpacc[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            bk[k] = ((a.fuse >> k) & 1) ? beta[k] : 0.0;
+            bk[k] = ((fuse >> k) & 1) ? beta[k] : 0.0;
             dpacc[k] = 0.0;
         }
         v4u pl[RING];
@@ -451,9 +496,9 @@ __device__ __forceinline__ void atax_team_body(const double* __restrict__ X, int
                             double t = sg * readlane_d(v, 32 * k);  // sigma_inv * dpa
                             t *= a.scale;                           // ATx[mloc] *= 1/sqrt(N)
                             double p = readlane_d(scv, 1 + k);
-                            if ((a.fuse >> k) & 1) p = readlane_d(scv, 1 + K + k) + bk[k] * p;  // p = z + beta p
-                            double val = t * a.tau;  // res[i] *= tau
-                            val += a.gam2 * p;       // res[i] += gam2 * v[i]
+                            if ((fuse >> k) & 1) p = readlane_d(scv, 1 + K + k) + bk[k] * p;  // p = z + beta p
+                            double val = t * sl.tau[k];  // res[i] *= tau
+                            val += sl.gam2[k] * p;       // res[i] += gam2 * v[i]
                             tsc[k] = t;
                             dval[k] = val;
                             pdir[k] = p;
@@ -465,8 +510,8 @@ __device__ __forceinline__ void atax_team_body(const double* __restrict__ X, int
 #pragma unroll
                             for (int k = 0; k < K; ++k) {
                                 if (lane == 0 && !(dbg & 1024)) {  // (timing experiment 1024: no d stores)
-                                    if (a.sraw.p[0]) a.sraw.p[k][mg] = tsc[k];
-                                    *tm_chk(a.d.p[k] + mg, a.d.p[k], a.d.p[k] + M, 128, a.err) = dval[k];
+                                    if (a.sraw.p[0]) sl.sraw[k][mg] = tsc[k];
+                                    *tm_chk(sl.d[k] + mg, sl.d[k], sl.d[k] + M, 128, a.err) = dval[k];
                                 }
                                 dpacc[k] += dval[k] * pdir[k];
                             }
@@ -509,6 +554,7 @@ __device__ __forceinline__ void atax_team_body(const double* __restrict__ X, int
     }
 
     // ---------------- the streaming waves ----------------
+    const TmSlots<K> sl = tm_slots<K>(a, alt);
     // q = A r/diag [+ beta*q_old] over the tile (each lane only reads its own rows)
 #pragma unroll
     for (int s = 0; s < S; ++s) {
@@ -521,8 +567,8 @@ __device__ __forceinline__ void atax_team_body(const double* __restrict__ X, int
                 double q = 0.0;
                 if (jl + h < nrows) {
                     const int64_t j = r0 + jl + h;
-                    q = a.ar.p[k][j] / a.diag;
-                    if ((a.fuse >> k) & 1) q = q + beta[k] * a.qo.p[k][j];
+                    q = sl.ar[k][j] / sl.diag[k];
+                    if ((fuse >> k) & 1) q = q + beta[k] * a.qo.p[k][j];
                 }
                 q_lds[k * QS + jl + h] = q;
             }
@@ -530,15 +576,15 @@ __device__ __forceinline__ void atax_team_body(const double* __restrict__ X, int
     }
     double bk[K];
 #pragma unroll
-    for (int k = 0; k < K; ++k) bk[k] = ((a.fuse >> k) & 1) ? beta[k] : 0.0;
+    for (int k = 0; k < K; ++k) bk[k] = ((fuse >> k) & 1) ? beta[k] : 0.0;
     // per-lane source of the column's scalars: lane 0 mave, 1 msig, 2.. p_k,
     // 2+K.. z_k, 2+2K.. the plain right-hand sides x_kp
     const double* pkp = mave;
     if (lane == 1) pkp = msig;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        if (lane == 2 + k) pkp = a.p.p[k];
-        if (lane == 2 + K + k && ((a.fuse >> k) & 1)) pkp = a.z.p[k];
+        if (lane == 2 + k) pkp = sl.p[k];
+        if (lane == 2 + K + k && ((fuse >> k) & 1)) pkp = a.z.p[k];
     }
 #pragma unroll
     for (int k = 0; k < KP; ++k)
@@ -674,13 +720,13 @@ __device__ __forceinline__ void atax_team_body(const double* __restrict__ X, int
                 double t = sg * tot[k];  // sigma_inv * dpa
                 t *= a.scale;            // ATx[mloc] *= 1/sqrt(N)
                 double p = readlane_d(pk[slot], 2 + k);
-                if ((a.fuse >> k) & 1) p = readlane_d(pk[slot], 2 + K + k) + bk[k] * p;  // p = z + beta p
-                double val = t * a.tau;  // res[i] *= tau
-                val += a.gam2 * p;       // res[i] += gam2 * v[i]
+                if ((fuse >> k) & 1) p = readlane_d(pk[slot], 2 + K + k) + bk[k] * p;  // p = z + beta p
+                double val = t * sl.tau[k];  // res[i] *= tau
+                val += sl.gam2[k] * p;       // res[i] += gam2 * v[i]
                 if (own) {
                     if (threadIdx.x == 0) {
-                        if (a.sraw.p[0]) a.sraw.p[k][mg] = t;
-                        a.d.p[k][mg] = val;
+                        if (a.sraw.p[0]) sl.sraw[k][mg] = t;
+                        sl.d[k][mg] = val;
                     }
                     dpacc[k] += val * p;
                 }
@@ -1042,9 +1088,19 @@ static hipError_t launch_tm_s(int S, const Shard& s, const OpPlan& pl, const OpA
     }
 }
 
+// the launch's slot table (OpAlt::tab): the K systems' values, then the alternate's
+static OpArgs tm_with_slots(const OpArgs& a, int K) {
+    OpArgs x = a;
+    for (int k = 0; k < K && k < kOpMaxK; ++k)
+        x.alt.tab[k] = OpAlt::Slot{a.ar.p[k], a.p.p[k], a.d.p[k], a.sraw.p[k], a.diag, a.tau, a.gam2};
+    x.alt.tab[kOpMaxK] = OpAlt::Slot{a.alt.ar, a.alt.p, a.alt.d, a.sraw.p[0] ? a.alt.d : nullptr, 1.0, 1.0, 0.0};
+    return x;
+}
+
 template <int K, bool PL = false>
-static hipError_t launch_tm_c(const Shard& s, const OpPlan& pl, const OpArgs& a, hipStream_t st, const Timing& tm,
+static hipError_t launch_tm_c(const Shard& s, const OpPlan& pl, const OpArgs& a0, hipStream_t st, const Timing& tm,
                         const int* gate, int* occ = nullptr) {
+    const OpArgs a = tm_with_slots(a0, K);
     if constexpr (PL) {
         switch (pl.cfg) {
             case 0: return launch_tm_s<1, 0, true>(pl.S, s, pl, a, st, tm, gate, occ);

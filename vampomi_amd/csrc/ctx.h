@@ -137,6 +137,12 @@ struct vampomi_ctx {
     bool hs_ok = false;       // the head start runs (hs_on included; agreed on several ranks)
     bool hs_on = true;
     bool hs_on_req = true;
+    // the pre-step (HeadStart below): 0 off, 1 on at any size, 2 auto (one
+    // rank, the linear model, the head start on and an X shard of at least
+    // kPreMinBytes); VAMPOMI_PRESTEP or vampomi_dev_set_variant(c, 7, v)
+    int pre_mode = 2;
+    unsigned long long pre_seq = 0;        // the last solve's token (OpAlt.token)
+    int64_t pre_made_n = 0, pre_used_n = 0;  // since vampomi_vamp_begin (vampomi_dev_prestep_counts)
     unsigned long long* op_ts = nullptr;  // VAMPOMI_OP_TS=1 (TM_TS builds): the last launch's workgroup times
     double* nbuf = nullptr;     // kMaxRhs * ld scratch N-vectors (API calls)
     double* mbuf = nullptr;     // (2*kMaxRhs) * M scratch M-vectors (API calls)
@@ -322,6 +328,20 @@ struct HeadStart {
     const double* xnext = nullptr;
     double* axnext = nullptr;
     bool used = false;  // out: the head start ran
+    // The PRE-STEP (one rank; kernels.h OpAlt, PreCompose).  In a step whose
+    // operator launch has a slot whose system has stopped, that slot forms
+    // T1 = A^T A xnext and U1 = A T1 (once per solve), the first CG step's
+    // products of the NEXT solve's system 0 up to its scalars.  With pre_have,
+    // this solve's system 0 takes its step 1 from them with no pass over X
+    // (vk::pre_compose), its step 2 rides in the head-start pass, and the
+    // solve takes 1 + max(k1 - 2, k2) passes.
+    double* T1 = nullptr;                  // M
+    double* U1 = nullptr;                  // ld
+    unsigned long long* pre_done = nullptr;  // device: the token of the last solve that made a pre-step
+    bool pre_have = false;   // in: T1, U1 hold the products of this solve's system 0 (with abern)
+    bool pre_offer = false;  // in: make them for the next solve (with xnext / axnext)
+    bool pre_made = false;   // out: made (for xnext)
+    bool pre_used = false;   // out: consumed
 };
 // pre (may be null; init must be null): the caller's prelude launch, fused
 // with the solve's start (vk::prelude_cg_init).  pm (one rank, with pre):
@@ -348,6 +368,12 @@ vampomi_status op_agree(vampomi_ctx* c);
 // whether pcg_run's head start can run on this context (plans the operator;
 // the same answer on every rank)
 vampomi_status headstart_available(vampomi_ctx* c, bool* yes);
+// the smallest X shard at which the auto pre-step turns on (bytes; never below
+// 256 MiB: the pinned default schedules of the small test shapes stay)
+constexpr int64_t kPreMinBytes = (int64_t)256 << 20;
+// whether the linear model's solves use the pre-step on this context (where
+// the head start is available): c->pre_mode resolved
+bool prestep_on(const vampomi_ctx* c);
 // the device word a team launch sets when a hand-off timed out, and its host view
 unsigned* op_err_dev(vampomi_ctx* c);
 vampomi_status op_check_err(vampomi_ctx* c);

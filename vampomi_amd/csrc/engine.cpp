@@ -1220,6 +1220,10 @@ extern "C" vampomi_status vampomi_open(const vampomi_shard_desc* d, vampomi_ctx*
     if (const char* mv = std::getenv("VAMPOMI_MR_TAIL")) c->mr_tail = c->mr_tail_req = std::atoi(mv) != 0;
     if (const char* fv = std::getenv("VAMPOMI_CG_FOLD")) c->cg_fold = std::atoi(fv) != 0;
     if (const char* hv = std::getenv("VAMPOMI_HEADSTART")) c->hs_on = c->hs_on_req = std::atoi(hv) != 0;
+    if (const char* pv = std::getenv("VAMPOMI_PRESTEP")) {
+        const int v = std::atoi(pv);
+        if (v >= 0 && v <= 2) c->pre_mode = v;
+    }
     const char* mode = std::getenv("VAMPOMI_COMM");
     if (c->use_comm && mode && std::strcmp(mode, "loopback") == 0) {
         if (!d->comm_id) return fail(VAMPOMI_ERR_ARG, "the loopback communicator needs a communicator id");
@@ -1820,6 +1824,9 @@ extern "C" vampomi_status vampomi_dev_set_variant(vampomi_ctx* c, int which, int
         if (variant != 0 && variant != 1) return fail(VAMPOMI_ERR_ARG, "head start: 0 or 1");
         c->hs_on_req = variant == 1;  // several ranks: applied and agreed at the next vampomi_vamp_begin
         if (!c->use_comm) c->hs_on = c->hs_on_req;
+    } else if (which == 7) {  // the pre-step (pcg.cpp): 0 off, 1 on at any size, 2 auto
+        if (variant < 0 || variant > 2) return fail(VAMPOMI_ERR_ARG, "pre-step: 0, 1 or 2");
+        c->pre_mode = variant;
     } else if (which == 6) {  // several ranks: the host-free iteration tail (vamp.cpp, VAMPOMI_MR_TAIL): 0 off, 1 on
         if (variant != 0 && variant != 1) return fail(VAMPOMI_ERR_ARG, "multi-rank tail: 0 or 1");
         c->mr_tail_req = variant == 1;  // agreed at the next vampomi_vamp_begin (it changes the collectives)
@@ -1828,6 +1835,18 @@ extern "C" vampomi_status vampomi_dev_set_variant(vampomi_ctx* c, int which, int
         if (!vk::loo_variant_ok(variant)) return fail(VAMPOMI_ERR_ARG, "no such association-pass variant");
         c->loo_variant = variant;
     }
+    return VAMPOMI_OK;
+}
+
+bool prestep_on(const vampomi_ctx* c) {
+    if (c->use_comm || c->nranks != 1 || !c->hs_ok || c->pre_mode == 0) return false;
+    return c->pre_mode == 1 || std::max<int64_t>(c->M, 1) * c->ld * 8 >= kPreMinBytes;
+}
+
+extern "C" vampomi_status vampomi_dev_prestep_counts(const vampomi_ctx* c, int64_t* made, int64_t* used) {
+    if (!c || !made || !used) return fail(VAMPOMI_ERR_ARG, "null argument");
+    *made = c->pre_made_n;
+    *used = c->pre_used_n;
     return VAMPOMI_OK;
 }
 
@@ -2029,6 +2048,7 @@ extern "C" vampomi_status vampomi_dev_mem_plan(int64_t N, int64_t Mt, int nranks
     for (int q = 0; q < 25; ++q) add(Mx, 8);           // VampRun M-vectors (15 + cgw[10])
     add(ld, 8), add((int64_t)vk::kMaxRhs * ld, 8), add((int64_t)vk::kMaxRhs * ld, 8), add(ld, 8);
     add(2 * ld, 8);                                    // abern (the head start, two slots)
+    add(Mx, 8), add(ld + 2, 8);                        // the pre-step's T1 and U1 (+ its done word)
     if (probit) {
         for (int q = 0; q < 3; ++q) add(ld, 8);
         for (int q = 0; q < 3; ++q) add(Mx, 8);

@@ -106,11 +106,11 @@ __device__ inline bool cg_decide_into(CgState& s, const double* red, int it, int
 // the decided state s to the host: pack: *flag receives the decision as one
 // word (cg_pack), no mirror; else the mirror slot (it & 1) then the flag
 __device__ inline void cg_publish(const CgState& s, bool ran, int it, CgMirror* mirror, unsigned long long* flag,
-                                  unsigned long long seq, int pack) {
+                                  unsigned long long seq, int pack, bool pre = false) {
     if (pack) {  // one word, one system-scope store: nothing to order
         if (flag && ran)
-            __hip_atomic_store(flag, cg_pack(seq, s.any, s.iters[0], s.iters[1]), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(flag, cg_pack(seq, s.any, s.iters[0], s.iters[1]) | (pre ? kCgPackPre : 0ull),
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         return;
     }
     // the mirror (mapped host memory) written through and drained, then the
@@ -134,10 +134,11 @@ __device__ inline void cg_publish(const CgState& s, bool ran, int it, CgMirror* 
 // written back once (a chain of dependent device loads and stores otherwise:
 // this runs at the end of every CG step), then published
 __device__ inline void cg_decide_from(CgState s, CgState* cs, const double* red, int it, CgMirror* mirror,
-                                      unsigned long long* flag, unsigned long long seq, int mask, int pack = 0) {
+                                      unsigned long long* flag, unsigned long long seq, int mask, int pack = 0,
+                                      bool pre = false) {
     const bool ran = cg_decide_into(s, red, it, mask);
     if (ran) *cs = s;
-    cg_publish(s, ran, it, mirror, flag, seq, pack);
+    cg_publish(s, ran, it, mirror, flag, seq, pack, pre);
 }
 
 __device__ inline void cg_decide_body(CgState* cs, const double* red, int it, CgMirror* mirror, unsigned long long* flag,

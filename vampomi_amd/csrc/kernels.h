@@ -179,6 +179,33 @@ struct OpFold {
     unsigned long long* flag = nullptr;
     unsigned long long seq = 0;
 };
+// The pre-step (pcg.cpp; one rank): an operator slot whose own system has
+// stopped carries the products T1 = A^T A b and A T1 of the NEXT Onsager
+// solve's right-hand side b instead of a discarded step.  Offered with cs set:
+// the launch's slot k = the lowest k < K with cs->active[k] == 0, if there is
+// one and *done != token (no pre-step made in this solve yet), runs with
+// ar_k = ar, p_k = p, d_k = d (= sraw_k), diag = tau = 1, gam2 = 0 and its
+// fuse bit cleared; its <d,p> means nothing.  Every workgroup reads the same
+// state (only cg_update's last block, after the launch, writes cs and done)
+struct OpAlt {
+    const CgState* cs = nullptr;
+    const unsigned long long* done = nullptr;
+    unsigned long long token = 0;
+    const double* ar = nullptr;  // A b (N-space, replicated)
+    const double* p = nullptr;   // any finite M-vector (b)
+    double* d = nullptr;         // T1 (M)
+    // filled by the launch (atax_team): slot k's pointers and scalars as the
+    // kernel reads them, k < K from OpArgs, entry kOpMaxK the alternate's (one
+    // indexed read per value instead of two candidates held in registers)
+    struct Slot {
+        const double* ar;
+        const double* p;
+        double* d;
+        double* sraw;
+        double diag, tau, gam2;
+    };
+    Slot tab[2 + 1];  // kOpMaxK + 1
+};
 struct OpArgs {
     CPtrs ar, qo;       // q_k = ar_k/diag [+ beta_k*qo_k when fuse] (N-space, replicated)
     CPtrs p, z;         // p_k [= z_k + beta_k*p_k when fuse] (M-space)
@@ -204,7 +231,9 @@ struct OpArgs {
               // 5 write-through hand-off even when the team shares an XCD, 11 no LDS q reads,
               // 12 no hand-off work (the hand-off wave only keeps the step barriers)
     OpFold fold;  // team kernels only (atax_team.hip)
+    OpAlt alt;    // team kernels only, never with fold.on or plain right-hand sides
 };
+static_assert(sizeof(OpAlt::tab) / sizeof(OpAlt::Slot) == kOpMaxK + 1, "one entry per system and the alternate's");
 std::string op_kernel_name(int K, const OpPlan& pl);
 std::string team_kernel_name(int K, const OpPlan& pl);
 // workgroups of the team kernel of plan pl (T >= 1) with K right-hand sides one
@@ -491,7 +520,23 @@ struct CgVecs {
     int64_t adld;
     int adslots;
     double addiv;
+    // the pre-step (OpAlt; with adpart only, may be null): when the step's
+    // operator launch ran slot k on the alternate system (the same rule, from
+    // the state and *pre_done this launch reads at its start), that slot's
+    // A d partials are summed into pre_u1 (the same order, / addiv) instead,
+    // and the last block stores pre_token into *pre_done and sets bit 31 of
+    // the packed decision word (kCgPackPre)
+    double* pre_u1;
+    unsigned long long* pre_done;
+    unsigned long long pre_token;
 };
+// the pre-step's slot for a launch on state s (OpAlt): -1 if none
+__host__ __device__ inline int cg_pre_slot(const int* active, int K, bool made) {
+    if (made) return -1;
+    for (int k = 0; k < K && k < kMaxRhs; ++k)
+        if (!active[k]) return k;
+    return -1;
+}
 // r = v - d (or v, or v - (atx0*tau + gam2*mu)), z = r/diag, p = z;
 // <r,z>, <v,v> per system in ro.out (2K values)
 hipError_t cg_init(int K, int64_t M, const CgVecs& c, double diag, const RedOut& ro, hipStream_t st);
@@ -522,6 +567,8 @@ __host__ __device__ inline unsigned long long cg_pack(unsigned long long seq, in
     return (seq << 32) | ((unsigned long long)(any ? 1 : 0) << 30) | ((unsigned long long)(it1 & 0x7fff) << 15) |
            (unsigned long long)(it0 & 0x7fff);
 }
+// bit 31 of the packed word: this step's launches made the pre-step (CgVecs.pre_u1)
+constexpr unsigned long long kCgPackPre = 1ull << 31;
 struct CgMirror {
     unsigned long long seq;  // the step's flag value: the slot holds that step's decision
     int any;
@@ -567,5 +614,23 @@ hipError_t cg_update(int K, int64_t M, const CgVecs& c, double diag, CgState* cs
 // stored when non-null, even when gated off)
 hipError_t cg_decide(CgState* cs, const double* red, int it, CgMirror* mirror, unsigned long long* flag,
                      unsigned long long seq, hipStream_t st, int mask = 0xf, int pack = 0);
+// The first CG step's operator products of a zero-start system with
+// right-hand side b, composed from T1 = A^T A b, U1 = A T1 and ab = A b (the
+// pre-step, OpAlt) with no pass over X.  p = b/diag as cg_init left it:
+//   t_i = T1_i/diag, d_i = tau*t_i + gam2*p_i, S_i = t_i (S may be null),
+//   AD_j = (tau*U1_j + gam2*ab_j)/diag, <d,p> in ro.out[0]
+// (A^T A is linear, so these are the step's d = tau*A^T A p + gam2*p and A d
+// up to rounding.)  Gated on ro.gate
+struct PreCompose {
+    const double* T1;  // M
+    const double* U1;  // N
+    const double* ab;  // N
+    const double* p;   // M
+    double* d;         // M
+    double* S;         // M, may be null
+    double* AD;        // N
+    double diag, tau, gam2;
+};
+hipError_t pre_compose(int64_t M, int64_t N, const PreCompose& a, const RedOut& ro, hipStream_t st);
 
 }  // namespace vk

@@ -2089,6 +2089,9 @@ __global__ __launch_bounds__(kBlock) void cg_update_kernel(int64_t M, CgVecs c, 
     }
 #endif
     if (!st.any) return;
+    // the pre-step (kernels.h OpAlt): the slot the step's operator launch ran on
+    // the alternate system, by the same rule from the same state (-1: none)
+    const int pre = c.pre_u1 ? cg_pre_slot(st.active, K, *c.pre_done == c.pre_token) : -1;
     __shared__ double fin[3 * kMaxRhs];  // the step's final sums, for the deciding thread
     // blocks [0, mblocks) stream the M-vectors; with c.adpart the blocks past
     // them sum the operator's A d partials and update the N-vectors
@@ -2214,6 +2217,10 @@ __global__ __launch_bounds__(kBlock) void cg_update_kernel(int64_t M, CgVecs c, 
                     if (c.AW[k]) c.AW[k][j] = awv[e] + alk * q;
                     c.AR[k][j] = arv[e] - ad[e] * alk;
                 }
+            } else if (w == 0 && ok && k == pre) {  // the alternate system's A d: the same sum, into U1
+                const v2d ad = (((wsum[0][lane] + wsum[1][lane]) + wsum[2][lane]) + wsum[3][lane]) / c.addiv;
+                c.pre_u1[i] = ad[0];
+                if (i + 1 < c.nA) c.pre_u1[i + 1] = ad[1];
             }
             __syncthreads();
         }
@@ -2274,8 +2281,10 @@ __global__ __launch_bounds__(kBlock) void cg_update_kernel(int64_t M, CgVecs c, 
         double r[3 * kMaxRhs];
 #pragma unroll
         for (int q = 0; q < 3 * kMaxRhs; ++q) r[q] = q < 3 * K ? fin[q] : 0.0;
-        cg_decide_from(st, cs, r, dc.it, dc.mirror, dc.flag, dc.seq, dc.mask, dc.pack);
+        cg_decide_from(st, cs, r, dc.it, dc.mirror, dc.flag, dc.seq, dc.mask, dc.pack, pre >= 0);
     }
+    // (every block read the done word before it took the ticket)
+    if (last && pre >= 0 && threadIdx.x == 0) *c.pre_done = c.pre_token;
 }
 
 constexpr int kCguBlocks = 512;
@@ -2324,6 +2333,42 @@ hipError_t cg_update(int K, int64_t M, const CgVecs& c, double diag, CgState* cs
 hipError_t cg_decide(CgState* cs, const double* red, int it, CgMirror* mirror, unsigned long long* flag,
                      unsigned long long seq, hipStream_t st, int mask, int pack) {
     hipLaunchKernelGGL(cg_decide_kernel, dim3(1), dim3(64), 0, st, cs, red, it, mirror, flag, seq, mask, pack);
+    return hipGetLastError();
+}
+
+// The pre-step's first CG step without a pass (kernels.h PreCompose).  The
+// expression order (no contraction: the file is built with -ffp-contract=off):
+//   t  = T1_i / diag                      (A^T A p, p = b/diag)
+//   d  = t * tau;  d += gam2 * p_i        (the lmmse_mult epilogue's two steps)
+//   S  = t
+//   AD = (tau * U1_j + gam2 * ab_j) / diag
+// <d,p>: per-block sums over i, i + stride, ... in order, then the blocks in
+// order (red_finish), as every reduction here
+__global__ __launch_bounds__(kBlock) void pre_compose_kernel(int64_t M, int64_t N, PreCompose a, RedOut ro) {
+    if (ro.gate && !*ro.gate) return;
+    __shared__ double lds[4];
+    double acc[1] = {0.0};
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < M; i += stride) {
+        const double t = a.T1[i] / a.diag;
+        const double p = a.p[i];
+        double d = t * a.tau;
+        d += a.gam2 * p;
+        a.d[i] = d;
+        if (a.S) a.S[i] = t;
+        acc[0] += d * p;
+    }
+    for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < N; j += stride) {
+        double u = a.tau * a.U1[j];
+        u += a.gam2 * a.ab[j];
+        a.AD[j] = u / a.diag;
+    }
+    block_put_sums<1>(acc, 1, ro, (int64_t)blockIdx.x);
+    red_finish(ro, 1, lds);
+}
+
+hipError_t pre_compose(int64_t M, int64_t N, const PreCompose& a, const RedOut& ro, hipStream_t st) {
+    hipLaunchKernelGGL(pre_compose_kernel, dim3(red_blocks(M)), dim3(kBlock), 0, st, M, N, a, ro);
     return hipGetLastError();
 }
 

@@ -33,6 +33,7 @@ static T* field(vk::CgState* cs, size_t off) {
 // The outcome of a decided CG step as the host reads it.
 struct CgOutcome {
     int any = 0;
+    bool pre = false;  // some decided step's launches made the pre-step (packed words only)
     int iters[vk::kMaxRhs] = {};
 };
 
@@ -74,6 +75,7 @@ static vampomi_status cg_loop(vampomi_ctx* c, int max_iter, bool packed, Enqueue
                 return fail(VAMPOMI_ERR_STATE, "CG step " + std::to_string(i - 1) + ": decision word holds sequence " +
                                                    std::to_string(w >> 32) + ", expected " + std::to_string(prev));
             o.any = (int)((w >> 30) & 1);
+            o.pre = last->pre || (w & vk::kCgPackPre) != 0;
             o.iters[0] = (int)(w & 0x7fff);
             o.iters[1] = (int)((w >> 15) & 0x7fff);
         } else {
@@ -107,6 +109,7 @@ vampomi_status pcg_run(vampomi_ctx* c, const std::vector<CgSystem*>& sys, double
     if (extra_x && (!ex_out || K + 1 >= vk::kMaxRhs)) return fail(VAMPOMI_ERR_ARG, "pcg: extra A.x needs K <= 2");
     if (hs) {
         hs->used = false;
+        hs->pre_made = hs->pre_used = false;
         if (!onepass || K != 2 || !extra_x || ar0 || sys[0]->mu0_nonzero || (hs->xnext && !hs->axnext))
             return fail(VAMPOMI_ERR_ARG, "pcg: the head start needs the one-pass form, two systems, extra_x, "
                                          "system 0 from zero and no ar0");
@@ -161,12 +164,16 @@ vampomi_status pcg_run(vampomi_ctx* c, const std::vector<CgSystem*>& sys, double
     // the head start (ctx.h, HeadStart): system 0's first step rides in the pass
     // that starts the solve; it is then one step ahead (CgState.off)
     const bool head = hs && hs->abern && c->hs_ok && c->op_ok && max_iter > 0;  // hs_ok: agreed, hs_on included
+    // the pre-step (ctx.h HeadStart): one rank, team plans, packed decisions
+    const bool pre_ok = hs && op1 && !c->use_comm && c->opp.T >= 1 && hs->T1 && hs->U1 && hs->pre_done &&
+                        max_iter > 0 && max_iter < vk::kCgPackMaxIter;
+    const bool pre2 = head && pre_ok && hs->pre_have;  // system 0's step 1 composed, its step 2 in the head pass
     vk::CgState s0{};
     s0.K = K;
     s0.gam2 = gam2;
     s0.tol = tol;
     s0.maxit = max_iter;
-    s0.off[0] = head ? 1 : 0;
+    s0.off[0] = head ? (pre2 ? 2 : 1) : 0;
     s0.any = max_iter > 0 ? 1 : 0;
     for (int k = 0; k < K; ++k) {
         s0.active[k] = 1;
@@ -315,6 +322,32 @@ vampomi_status pcg_run(vampomi_ctx* c, const std::vector<CgSystem*>& sys, double
             for (int k = 0; k < K; ++k)
                 if (!sys[k]->S) return fail(VAMPOMI_ERR_ARG, "pcg: W needs an S scratch vector for every system");
         const int all = (1 << K) - 1;
+        if (pre2) {
+            // system 0's step 1 (it = -2) from T1, U1 and A r0 = abern: no pass
+            vk::PreCompose pc{};
+            pc.T1 = hs->T1;
+            pc.U1 = hs->U1;
+            pc.ab = cu.AR[0];
+            pc.p = sys[0]->p;
+            pc.d = sys[0]->d;
+            pc.S = rec ? sys[0]->S : nullptr;
+            pc.AD = const_cast<double*>(cu.AD[0]);
+            pc.diag = diag;
+            pc.tau = tau;
+            pc.gam2 = gam2;
+            HIPCHK(vk::pre_compose(M, N, pc, vk::RedOut{c->red_part, c->scal + SL_DP, c->ticket, nullptr, 0, gate},
+                                   c->st));
+            vk::CgVecs cp = cu;  // A d is the composed vector, whole
+            cp.adpart = nullptr;
+            cp.addiv = 0.0;
+            const vk::RedOut ro{c->red_part, c->scal + SL_CG, c->ticket, nullptr, 0, gate};
+            vk::CgDecide dc{};  // no mirror, no flag: the host does not wait for this step
+            dc.on = 1;
+            dc.it = -2;
+            dc.mask = 1;
+            HIPCHK(vk::cg_update(1, M, cp, diag, c->cgs, c->scal + SL_DP, nullptr, 0, ro, dc, c->st));
+            hs->pre_used = true;
+        }
         if (head) {
             // system 0's step 1 (it = -1: its count becomes 1 + off - 1 + ... = 1)
             // together with A r0 of system 1, A extra_x and A xnext: one pass
@@ -326,7 +359,7 @@ vampomi_status pcg_run(vampomi_ctx* c, const std::vector<CgSystem*>& sys, double
             a.d.p[0] = sys[0]->d;
             a.sraw.p[0] = rec ? sys[0]->S : nullptr;
             a.beta = beta;
-            a.fuse = 0;
+            a.fuse = pre2 ? 1 : 0;  // (its step 2: the direction update of step 1 rides in)
             a.diag = diag;
             a.tau = tau;
             a.gam2 = gam2;
@@ -342,7 +375,7 @@ vampomi_status pcg_run(vampomi_ctx* c, const std::vector<CgSystem*>& sys, double
             dc.on = !c->use_comm;
             dc.it = -1;
             dc.mask = 1;
-            HIPCHK(vk::cg_update(1, M, ch, diag, c->cgs, dp, nullptr, 0, ro, dc, c->st));
+            HIPCHK(vk::cg_update(1, M, ch, diag, c->cgs, dp, nullptr, pre2 ? 1 : 0, ro, dc, c->st));
             if (c->use_comm) {
                 STCHK(allreduce_dev(c, c->scal + SL_CG, 3));
                 if (fold) {  // formed by step 0's operator launch
@@ -358,6 +391,15 @@ vampomi_status pcg_run(vampomi_ctx* c, const std::vector<CgSystem*>& sys, double
         // the decisions travel as one packed word each (cg_loop): one
         // system-scope store instead of the mirror's six, a drain and the flag
         const bool packed = K <= 2 && max_iter < vk::kCgPackMaxIter;
+        // the pre-step for the next solve: offered to every regular step
+        const bool offer = pre_ok && packed && hs->pre_offer && hs->xnext && hs->axnext && !fold;
+        const unsigned long long token = offer ? ++c->pre_seq : 0;
+        vk::CgVecs cuo = cu;
+        if (offer) {
+            cuo.pre_u1 = hs->U1;
+            cuo.pre_done = hs->pre_done;
+            cuo.pre_token = token;
+        }
         auto enqueue = [&](int i, unsigned long long* seq) -> vampomi_status {
             // the direction updates fused into step i: every system's from step
             // 1 on; at step 0 those of the systems already under way (head start)
@@ -372,6 +414,14 @@ vampomi_status pcg_run(vampomi_ctx* c, const std::vector<CgSystem*>& sys, double
                 a.sraw.p[k] = rec ? sys[k]->S : nullptr;
             }
             a.beta = fold ? nullptr : beta;
+            if (offer) {
+                a.alt.cs = c->cgs;
+                a.alt.done = hs->pre_done;
+                a.alt.token = token;
+                a.alt.ar = hs->axnext;
+                a.alt.p = hs->xnext;
+                a.alt.d = hs->T1;
+            }
             a.fuse = fuse;
             a.diag = diag;
             a.tau = tau;
@@ -412,7 +462,7 @@ vampomi_status pcg_run(vampomi_ctx* c, const std::vector<CgSystem*>& sys, double
                 dc.seq = *seq;
                 dc.pack = packed ? 1 : 0;
             }
-            HIPCHK(vk::cg_update(K, M, cu, diag, cs, dp, nullptr, fuse, ro, dc, c->st));
+            HIPCHK(vk::cg_update(K, M, cuo, diag, cs, dp, nullptr, fuse, ro, dc, c->st));
             if (c->use_comm) {
                 STCHK(allreduce_dev(c, c->scal + SL_CG, (size_t)(3 * K)));
                 if (fold) {  // formed by the next step's operator launch (or settle)
@@ -444,6 +494,7 @@ vampomi_status pcg_run(vampomi_ctx* c, const std::vector<CgSystem*>& sys, double
             sys[k]->iters = last.iters[k];
             if (ref_passes) *ref_passes += 2 * (int64_t)sys[k]->iters;
         }
+        if (offer) hs->pre_made = last.pre;
         return VAMPOMI_OK;
     }
     if (xnext) {  // (no one-pass plan: the head start's next product by its own pass)

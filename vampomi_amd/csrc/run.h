@@ -64,6 +64,10 @@ struct VampRun {
     double* ax2 = nullptr;  // arec: A x2, carried from iteration to iteration
     double* abern = nullptr;      // the head start: A.bern of iteration hs_it in slot hs_it & 1 (2 x ld)
     double* bern_next = nullptr;  // ... and the next iteration's probe (M)
+    // the pre-step (ctx.h HeadStart): T1 = A^T A bern and U1 = A T1 (+ the done word) of iteration pre_it
+    double* pre_t1 = nullptr;
+    double* pre_u1 = nullptr;
+    int pre_it = 0;
     // the device EM update (vk::EmArgs.upd): the mixture it formed (device
     // words, read by the next denoising) and its mapped host mirror, checked
     // against the host's update (mix_expect) once a later launch has flagged

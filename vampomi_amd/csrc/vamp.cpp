@@ -49,7 +49,7 @@
 VampRun::~VampRun() {
     if (writer) writer->drain(nullptr);  // its kernels read x1 / r1, its thread writes the caller's history arrays
     for (double** p : {&r1, &x1, &x1p, &x1n, &x1d, &r2, &x2, &bern, &invQ, &v, &atxy, &ts, &tmpM, &atx0, &z1buf,
-                       &nb3, &nsc, &ax2, &p1, &p2, &z1h, &x1s, &x1sn, &x2s, &abern, &bern_next})
+                       &nb3, &nsc, &ax2, &p1, &p2, &z1h, &x1s, &x1sn, &x2s, &abern, &bern_next, &pre_t1, &pre_u1})
         dev_free(*p);
     for (auto& p : cgw) dev_free(p);
     dev_free(mixw);
@@ -258,6 +258,11 @@ static vampomi_status vamp_alloc(vampomi_ctx* c, VampRun& R) {
     STCHK(dev_alloc(&R.nsc, vk::kMaxRhs * ld));
     STCHK(dev_alloc(&R.ax2, ld));
     STCHK(dev_alloc(&R.abern, 2 * ld));  // two slots: A.bern of it (consumed in place) and of it + 1
+    // the pre-step's products (ctx.h HeadStart): T1 (M), U1 (ld) and, behind U1, its done word
+    STCHK(dev_alloc(&R.pre_t1, M));
+    STCHK(dev_alloc(&R.pre_u1, ld + 2));
+    HIPCHK(hipMemsetAsync(R.pre_t1, 0, M * 8, c->st));
+    HIPCHK(hipMemsetAsync(R.pre_u1, 0, (ld + 2) * 8, c->st));
     STCHK(dev_alloc(&R.mixw, vk::kMixWords));
     HIPCHK(hipHostMalloc((void**)&R.mixh, (vk::kMixWords + 4) * sizeof(double),
                          hipHostMallocMapped | hipHostMallocCoherent));
@@ -285,6 +290,7 @@ extern "C" vampomi_status vampomi_vamp_begin(vampomi_ctx* c, const vampomi_param
     HIPCHK(hipSetDevice(c->device));
     STCHK(op_agree(c));  // several ranks: the one-pass / head-start choice, agreed here, where every rank is
     c->run.reset(new VampRun());
+    c->pre_made_n = c->pre_used_n = 0;  // (a new run: no pre-step products carried over, VampRun.pre_it = 0)
     VampRun& R = *c->run;
     R.prm = *p;
     R.res = r;
@@ -502,6 +508,13 @@ static vampomi_status lmmse_setup(vampomi_ctx* c, VampRun& R, int it, const doub
             L.hs.xnext = R.bern_next;  // the probe of it + 1, formed by the prelude below
             L.hs.axnext = R.abern + ((it + 1) & 1) * ld;
         }
+        if (prestep_on(c)) {  // (one rank: the head start's conditions hold)
+            L.hs.T1 = R.pre_t1;
+            L.hs.U1 = R.pre_u1;
+            L.hs.pre_done = reinterpret_cast<unsigned long long*>(R.pre_u1 + ld);
+            L.hs.pre_have = L.hs.abern && R.pre_it == it;
+            L.hs.pre_offer = L.hs.xnext != nullptr;
+        }
     }
     // the iteration's elementwise work before the CG solves, in one launch
     // (it replaces five: r2, bern, v, and the zeroed invQ (:496) and its W)
@@ -623,12 +636,17 @@ extern "C" vampomi_status vampomi_vamp_step(vampomi_ctx* c, int* stopped) {
         STCHK(pcg_run(c, {&so, &sx}, R.gamw, R.gam2, R.prm.CG_max_iter, R.prm.CG_err_tol, R.nsc, &R.passes_ref,
                       nullptr, R.x1, R.z1buf, true, nullptr, &hs, &pr, pm));
         R.hs_it = hs.xnext ? it + 1 : 0;
+        // T1, U1 made by this solve are the next one's (consumed before that solve refills them)
+        R.pre_it = hs.pre_made ? it + 1 : 0;
+        c->pre_made_n += hs.pre_made ? 1 : 0;
+        c->pre_used_n += hs.pre_used ? 1 : 0;
     } else if (R.fuse) {
         STCHK(pcg_run(c, {&sx, &so}, R.gamw, R.gam2, R.prm.CG_max_iter, R.prm.CG_err_tol, R.nsc, &R.passes_ref,
                       arec ? nullptr : &e1, arec ? R.x1 : nullptr, arec ? R.z1buf : nullptr, R.onepass, nullptr,
                       nullptr, arec ? &pr : nullptr));
-        R.hs_it = 0;
+        R.hs_it = R.pre_it = 0;
     } else {
+        R.pre_it = 0;
         STCHK(pcg_run(c, {&sx}, R.gamw, R.gam2, R.prm.CG_max_iter, R.prm.CG_err_tol, R.nsc, &R.passes_ref, &e1));
         STCHK(pcg_run(c, {&so}, R.gamw, R.gam2, R.prm.CG_max_iter, R.prm.CG_err_tol, R.nsc, &R.passes_ref, nullptr));
     }
