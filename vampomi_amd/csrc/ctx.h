@@ -81,6 +81,7 @@ struct vampomi_ctx {
     double coll_limit_s = 0.0;  // > 0: the limit of the collective in progress (vampomi_barrier_timeout)
     bool mr_tail_req = true;  // this rank's VAMPOMI_MR_TAIL (0: off), agreed over the ranks by op_agree
     bool cg_fold = true;   // several ranks: each CG decision formed by the next operator launch (pcg.cpp); VAMPOMI_CG_FOLD=0
+    bool dp_separate = false;  // several ranks, two-pass CG: <d,p> by its own reduction, the one-rank form (pcg.cpp); VAMPOMI_DP_SEPARATE=1
     bool team_reg = false;           // registered with its device's team gate (engine.cpp)
     hipEvent_t team_ev = nullptr;    // recorded on st when another context must order behind it
     ncclComm_t comm = nullptr;
@@ -300,28 +301,16 @@ struct CgSystem {
     int iters = 0;
     double *r = nullptr, *z = nullptr, *p = nullptr, *d = nullptr;  // work vectors (device, M)
 };
-// Solves the systems together: every CG step streams X twice for all still
-// active systems; each keeps its own scalars and stopping rule.  `init` (may
-// be null) is flushed together with the initial residual reductions.
-// extra_x (may be null, device M): ex_out (device, ld) = A extra_x, carried as
-// one more right-hand side of the first step's A.x pass (its own pass if no
-// step runs).  nscratch holds kMaxRhs*ld + kMaxRhs doubles.
-// onepass (K <= 2): every CG step reads X once (vk::atax; A r0 by one A.x pass
-// per solve, which also carries extra_x); otherwise two passes per step.
-// ar0 (may be null; onepass only): ar0[k] (device, ld, may be null) already
-// holds A r0 of system k (its start is zero, so r0 = v), and the first A.x
-// pass covers only the systems without it (no pass if none).
-//
-// hs (may be null; onepass, K = 2, extra_x): the HEAD START.  System 0 must
+// The HEAD START (PcgArgs::hs; onepass, K = 2, extra_x).  System 0 must
 // start from zero (r0 = v, e.g. the Onsager solve, whose v is a probe known an
-// iteration early).  hs->abern (device ld) holds A v of system 0: then system
+// iteration early).  abern (device ld) holds A v of system 0: then system
 // 0's first CG step runs in the pass that would only compute A r0 of system 1
 // and A extra_x (one operator launch with plain right-hand sides,
 // op_dev_plain), and the two systems step together from there, system 0 one
 // step ahead, so the solve takes 1 + max(k1 - 1, k2) passes instead of
 // 1 + max(k1, k2).  Every step is the reference's (src/vamp.cpp:697-757).
-// hs->xnext (may be null, device M): one more right-hand side of that pass,
-// hs->axnext = A xnext (the next solve's abern).  Without hs->abern the first
+// xnext (may be null, device M): one more right-hand side of that pass,
+// axnext = A xnext (the next solve's abern).  Without abern the first
 // A.x pass carries xnext instead.
 struct HeadStart {
     double* abern = nullptr;  // (the Onsager solve's A r: updated in place)
@@ -343,17 +332,42 @@ struct HeadStart {
     bool pre_made = false;   // out: made (for xnext)
     bool pre_used = false;   // out: consumed
 };
-// pre (may be null; init must be null): the caller's prelude launch, fused
-// with the solve's start (vk::prelude_cg_init).  pm (one rank, with pre):
-// ahead: queue only that launch, its scalars from the device (pre->dev; tau
-// and gam2 unused), and return; queued: that launch was queued ahead (the same
-// sys, hs and pre): the solve goes on after it
+// how PcgArgs::pre's launch is queued (one rank)
 enum class PreMode { normal, ahead, queued };
-vampomi_status pcg_run(vampomi_ctx* c, const std::vector<CgSystem*>& sys, double tau, double gam2, int max_iter,
-                       double tol, double* nscratch, int64_t* ref_passes, DotBatch* init,
-                       const double* extra_x = nullptr, double* ex_out = nullptr, bool onepass = false,
-                       const double* const* ar0 = nullptr, HeadStart* hs = nullptr,
-                       const vk::Prelude* pre = nullptr, PreMode pm = PreMode::normal);
+// pcg_run's arguments beside the systems (tau*A^T A + gam2*I) mu = v
+struct PcgArgs {
+    double tau = 0.0, gam2 = 0.0;
+    int max_iter = 0;    // CG steps per system at most
+    double tol = 0.0;    // a system stops when ||r||/||v|| < tol
+    double* nscratch = nullptr;     // device scratch, kMaxRhs*ld + kMaxRhs doubles
+    int64_t* ref_passes = nullptr;  // (may be null) += the passes over X the reference would have made
+    // (may be null) flushed together with the initial residual reductions (one host wait)
+    DotBatch* init = nullptr;
+    // extra_x (may be null, device M): ex_out (device, ld) = A extra_x, carried as
+    // one more right-hand side of the first step's A.x pass (its own pass if no
+    // step runs); K <= 2
+    const double* extra_x = nullptr;
+    double* ex_out = nullptr;
+    // (K <= 2) every CG step reads X once (vk::atax; A r0 by one A.x pass per
+    // solve, which also carries extra_x); otherwise two passes per step
+    bool onepass = false;
+    // (may be null; onepass only) ar0[k] (device, ld, may be null) already
+    // holds A r0 of system k (its start is zero, so r0 = v), and the first A.x
+    // pass covers only the systems without it (no pass if none)
+    const double* const* ar0 = nullptr;
+    HeadStart* hs = nullptr;  // the head start above (may be null; onepass, K = 2, extra_x, system 0 at zero, no ar0)
+    // pre (may be null; init must be null): the caller's prelude launch, fused
+    // with the solve's start (vk::prelude_cg_init).  pm (one rank, with pre):
+    // ahead: queue only that launch, its scalars from the device (pre->dev; tau
+    // and gam2 unused), and return; queued: that launch was queued ahead (the same
+    // sys, hs and pre): the solve goes on after it
+    const vk::Prelude* pre = nullptr;
+    PreMode pm = PreMode::normal;
+};
+// Solves the systems together: every CG step streams X twice (once with
+// onepass) for all still active systems; each keeps its own scalars and
+// stopping rule.  The arguments are checked before anything is queued
+vampomi_status pcg_run(vampomi_ctx* c, const std::vector<CgSystem*>& sys, const PcgArgs& args);
 // plans the one-pass operator on this rank (c->opp, op_ok_mine, hs_ok_mine)
 // and allocates its buffers (idempotent until the plan or the head-start
 // switch changes); never a collective.  Sets op_ok / hs_ok: this rank's plan

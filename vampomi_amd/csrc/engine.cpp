@@ -1219,6 +1219,7 @@ extern "C" vampomi_status vampomi_open(const vampomi_shard_desc* d, vampomi_ctx*
     c->use_comm = c->nranks > 1 || (force && std::atoi(force) != 0);
     if (const char* mv = std::getenv("VAMPOMI_MR_TAIL")) c->mr_tail = c->mr_tail_req = std::atoi(mv) != 0;
     if (const char* fv = std::getenv("VAMPOMI_CG_FOLD")) c->cg_fold = std::atoi(fv) != 0;
+    if (const char* dv = std::getenv("VAMPOMI_DP_SEPARATE")) c->dp_separate = std::atoi(dv) != 0;
     if (const char* hv = std::getenv("VAMPOMI_HEADSTART")) c->hs_on = c->hs_on_req = std::atoi(hv) != 0;
     if (const char* pv = std::getenv("VAMPOMI_PRESTEP")) {
         const int v = std::atoi(pv);
@@ -1615,7 +1616,13 @@ extern "C" vampomi_status vampomi_pcg(vampomi_ctx* c, const double* v, const dou
         HIPCHK(hipMemsetAsync(s.mu, 0, (size_t)Mx * 8, c->st));
     else
         STCHK(stage_in(c, mu0, c->M, mem, s.mu));
-    STCHK(pcg_run(c, {&s}, tau, gam2, max_iter, tol, c->nbuf, nullptr, nullptr));
+    PcgArgs a;
+    a.tau = tau;
+    a.gam2 = gam2;
+    a.max_iter = max_iter;
+    a.tol = tol;
+    a.nscratch = c->nbuf;
+    STCHK(pcg_run(c, {&s}, a));
     STCHK(stage_out(c, s.mu, c->M, mem, mu));
     if (iters) *iters = s.iters;
     if (c->timing) resolve_timing(c);

@@ -191,12 +191,20 @@ vampomi_status probit_step(vampomi_ctx* c, VampRun& R) {
     HIPCHK(hipMemsetAsync(R.x2, 0, Mb, c->st));
     HIPCHK(hipMemsetAsync(R.invQ, 0, Mb, c->st));
     const auto t_solve = std::chrono::steady_clock::now();
+    PcgArgs pargs;
+    pargs.tau = R.tau2;
+    pargs.gam2 = R.gam2;
+    pargs.max_iter = R.prm.CG_max_iter;
+    pargs.tol = R.prm.CG_err_tol;
+    pargs.nscratch = R.nsc;
+    pargs.ref_passes = &R.passes_ref;
     if (R.fuse) {
-        STCHK(pcg_run(c, {&sx, &so}, R.tau2, R.gam2, R.prm.CG_max_iter, R.prm.CG_err_tol, R.nsc, &R.passes_ref,
-                      nullptr, nullptr, nullptr, R.onepass, merged ? ar0 : nullptr));
+        pargs.onepass = R.onepass;
+        if (merged) pargs.ar0 = ar0;
+        STCHK(pcg_run(c, {&sx, &so}, pargs));
     } else {
-        STCHK(pcg_run(c, {&sx}, R.tau2, R.gam2, R.prm.CG_max_iter, R.prm.CG_err_tol, R.nsc, &R.passes_ref, nullptr));
-        STCHK(pcg_run(c, {&so}, R.tau2, R.gam2, R.prm.CG_max_iter, R.prm.CG_err_tol, R.nsc, &R.passes_ref, nullptr));
+        STCHK(pcg_run(c, {&sx}, pargs));
+        STCHK(pcg_run(c, {&so}, pargs));
     }
     R.ph_solve_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_solve).count();
     if (res && res->cg_iters) res->cg_iters[it - 1] = sx.iters;

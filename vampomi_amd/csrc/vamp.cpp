@@ -632,23 +632,43 @@ extern "C" vampomi_status vampomi_vamp_step(vampomi_ctx* c, int* stopped) {
         return fail(VAMPOMI_ERR_STATE, "vamp: the start queued ahead does not match this iteration's schedule");
     if (!L.pre_in_cg) HIPCHK(vk::prelude(M, pr, c->st));
     const auto t_solve = std::chrono::steady_clock::now();
+    PcgArgs pargs;  // what this iteration's solves share
+    pargs.tau = R.gamw;
+    pargs.gam2 = R.gam2;
+    pargs.max_iter = R.prm.CG_max_iter;
+    pargs.tol = R.prm.CG_err_tol;
+    pargs.nscratch = R.nsc;
+    pargs.ref_passes = &R.passes_ref;
     if (R.fuse && hs_av) {
-        STCHK(pcg_run(c, {&so, &sx}, R.gamw, R.gam2, R.prm.CG_max_iter, R.prm.CG_err_tol, R.nsc, &R.passes_ref,
-                      nullptr, R.x1, R.z1buf, true, nullptr, &hs, &pr, pm));
+        pargs.extra_x = R.x1;
+        pargs.ex_out = R.z1buf;
+        pargs.onepass = true;
+        pargs.hs = &hs;
+        pargs.pre = &pr;
+        pargs.pm = pm;
+        STCHK(pcg_run(c, {&so, &sx}, pargs));
         R.hs_it = hs.xnext ? it + 1 : 0;
         // T1, U1 made by this solve are the next one's (consumed before that solve refills them)
         R.pre_it = hs.pre_made ? it + 1 : 0;
         c->pre_made_n += hs.pre_made ? 1 : 0;
         c->pre_used_n += hs.pre_used ? 1 : 0;
     } else if (R.fuse) {
-        STCHK(pcg_run(c, {&sx, &so}, R.gamw, R.gam2, R.prm.CG_max_iter, R.prm.CG_err_tol, R.nsc, &R.passes_ref,
-                      arec ? nullptr : &e1, arec ? R.x1 : nullptr, arec ? R.z1buf : nullptr, R.onepass, nullptr,
-                      nullptr, arec ? &pr : nullptr));
+        if (arec) {
+            pargs.extra_x = R.x1;
+            pargs.ex_out = R.z1buf;
+            pargs.pre = &pr;
+        } else {
+            pargs.init = &e1;
+        }
+        pargs.onepass = R.onepass;
+        STCHK(pcg_run(c, {&sx, &so}, pargs));
         R.hs_it = R.pre_it = 0;
     } else {
         R.pre_it = 0;
-        STCHK(pcg_run(c, {&sx}, R.gamw, R.gam2, R.prm.CG_max_iter, R.prm.CG_err_tol, R.nsc, &R.passes_ref, &e1));
-        STCHK(pcg_run(c, {&so}, R.gamw, R.gam2, R.prm.CG_max_iter, R.prm.CG_err_tol, R.nsc, &R.passes_ref, nullptr));
+        PcgArgs first = pargs;
+        first.init = &e1;
+        STCHK(pcg_run(c, {&sx}, first));
+        STCHK(pcg_run(c, {&so}, pargs));
     }
     R.ph_solve_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_solve).count();
     STCHK(check_device_values(c, R, it));  // (the solves' flags came after the previous iteration's launches)
@@ -853,8 +873,17 @@ extern "C" vampomi_status vampomi_vamp_step(vampomi_ctx* c, int* stopped) {
     if (!shared) STCHK(fin.add_many(M, {gnm}));  // NMSE (:409-413)
     // iteration it+1's prelude and solves' start, queued now (set up above)
     if (ahead) {
-        STCHK(pcg_run(c, {&A.so, &A.sx}, 0.0, 0.0, R.prm.CG_max_iter, R.prm.CG_err_tol, R.nsc, nullptr, nullptr,
-                      R.x1n, R.z1buf, true, nullptr, &A.hs, &A.pr, PreMode::ahead));
+        PcgArgs pargs;  // (tau and gam2 come from the device)
+        pargs.max_iter = R.prm.CG_max_iter;
+        pargs.tol = R.prm.CG_err_tol;
+        pargs.nscratch = R.nsc;
+        pargs.extra_x = R.x1n;
+        pargs.ex_out = R.z1buf;
+        pargs.onepass = true;
+        pargs.hs = &A.hs;
+        pargs.pre = &A.pr;
+        pargs.pm = PreMode::ahead;
+        STCHK(pcg_run(c, {&A.so, &A.sx}, pargs));
         R.pre_ahead = it + 1;
     }
     STCHK(fin.flush());
