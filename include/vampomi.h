@@ -73,6 +73,15 @@ typedef enum {
 #define VAMPOMI_GEN_GAUSS 0       /* i.i.d. N(0,1)-like (simulation/data_sim.py:35) */
 #define VAMPOMI_GEN_METH 1        /* methylation-like beta values in [0,1] */
 
+/* how the methylation shard is held on the device (vampomi_set_storage).  The
+ * matrix is the only object whose size matters, and every pass is bound by
+ * reading it: as floats it takes half the memory and half the bytes per pass.
+ * Only the storage changes: every sum, the CG, the denoiser, EM and p-values
+ * stay fp64, and an F32 context computes, bit for bit, what an F64 context
+ * computes on the widened copy of the same stored values. */
+#define VAMPOMI_STORE_F64 0       /* doubles (the default; the reference's file format) */
+#define VAMPOMI_STORE_F32 1       /* floats: fp64 input is rounded to nearest even at ingest */
+
 typedef struct vampomi_ctx vampomi_ctx;
 
 typedef struct {
@@ -115,11 +124,32 @@ vampomi_status vampomi_all_ok(vampomi_ctx* ctx, int local_ok, int* all_ok);
 vampomi_status vampomi_comm_abort(vampomi_ctx* ctx);
 
 /* ---- data ingest (data::data) ---- */
-/* marker-major fp64 file (README.md:15): this shard's bytes [S*N*8, (S+M)*N*8) */
+/* The storage of the shard, VAMPOMI_STORE_F64 (the default) or _F32.  Legal
+ * only before the shard is allocated, i.e. before any vampomi_load_meth_* or
+ * vampomi_generate_meth: VAMPOMI_ERR_STATE afterwards, VAMPOMI_ERR_ARG for
+ * any other value.  VAMPOMI_STORAGE=f32|f64 in the environment sets the default
+ * at vampomi_open (any other value: vampomi_open fails with VAMPOMI_ERR_ARG).
+ * Rank-local: the ranks of a job need not agree on it.  The column stride ld
+ * (elements) and every kernel plan are the same for both storages. */
+vampomi_status vampomi_set_storage(vampomi_ctx* ctx, int storage);
+vampomi_status vampomi_get_storage(const vampomi_ctx* ctx, int* storage);
+/* marker-major fp64 file (README.md:15): this shard's bytes [S*N*8, (S+M)*N*8).
+ * On an F32 context each chunk is staged on the device as fp64 and rounded
+ * there (nearest even) into the column layout. */
 vampomi_status vampomi_load_meth_file(vampomi_ctx* ctx, const char* path);
-/* host shard: M columns of N samples, column stride ld_in >= N doubles */
+/* the same marker-major layout with 4-byte float elements: this shard's bytes
+ * [S*N*4, (S+M)*N*4), through the same read pipeline; widened (exactly) on an
+ * F64 context */
+vampomi_status vampomi_load_meth_file_f32(vampomi_ctx* ctx, const char* path);
+/* host shard: M columns of N samples, column stride ld_in >= N doubles
+ * (rounded on the device on an F32 context) */
 vampomi_status vampomi_load_meth_host(vampomi_ctx* ctx, const double* X, int64_t ld_in);
-/* synthetic shard generated on the device (bit-identical to the oracle's) */
+/* host shard of floats, column stride ld_in >= N floats, for either storage
+ * (widened exactly on an F64 context) */
+vampomi_status vampomi_load_meth_host_f32(vampomi_ctx* ctx, const float* X, int64_t ld_in);
+/* synthetic shard generated on the device (bit-identical to the oracle's; an
+ * F32 context stores the generator's value rounded: VAMPOMI_GEN_GAUSS values
+ * are exactly floats, VAMPOMI_GEN_METH values are not) */
 vampomi_status vampomi_generate_meth(vampomi_ctx* ctx, uint64_t seed, int kind);
 /* PLINK phenotype, standardize = scale to unit variance, NOT centred */
 vampomi_status vampomi_read_phen(vampomi_ctx* ctx, const char* path, int standardize);
@@ -135,9 +165,11 @@ vampomi_status vampomi_simulate_phen(vampomi_ctx* ctx, uint64_t seed, double lam
  * src/data.cpp:40-41). COLLECTIVE */
 vampomi_status vampomi_simulate_phen_binary(vampomi_ctx* ctx, uint64_t seed, double lam, double h2,
                                             double* beta_out);
+/* (the statistics of the STORED values, accumulated in fp64) */
 vampomi_status vampomi_get_marker_stats(vampomi_ctx* ctx, double* mave, double* msig);
 /* copy local markers [i0, i0+count) back to the host, count x N doubles
- * (data::get_meth_data, src/data.hpp:53) */
+ * (data::get_meth_data, src/data.hpp:53); an F32 context returns the stored
+ * values widened, each exactly a float */
 vampomi_status vampomi_read_markers(vampomi_ctx* ctx, int64_t i0, int64_t count, double* out);
 
 /* ---- operators ---- */
@@ -342,7 +374,8 @@ vampomi_status vampomi_dev_prestep_counts(const vampomi_ctx* ctx, int64_t* made,
 /* average device time (HIP events) of `reps` back-to-back launches, K RHS */
 vampomi_status vampomi_dev_time_pass(vampomi_ctx* ctx, int which, int K, int reps, double* avg_ms);
 /* The HBM read ceiling of this device for this shard: a pure read stream of
- * the resident matrix (every byte once, 16-byte nontemporal loads; variant 0
+ * the resident matrix (every byte once, 16-byte nontemporal loads, 8-byte ones
+ * of an F32 context's floats: *bytes is what is resident; variant 0
  * lockstep 8-wave workgroups, one per CU, variant 1 a 1 MiB contiguous chunk
  * per wave), `reps` timed launches of each; the faster variant's median launch
  * time in *us_med, the bytes it read in *bytes, the variant in *variant.  No
@@ -352,6 +385,8 @@ vampomi_status vampomi_dev_read_ceiling(vampomi_ctx* ctx, int reps, double* us_m
  * (mode 1: the CG form, i.e. A^T.u with the lmmse_mult epilogue, A.x with the
  * fused direction update; which = 2: the association-test pass of
  * vampomi_assoc_loo) */
+/* (an F32 context launches the fp32 entry points: the same names with an _f32
+ * suffix before the template arguments) */
 vampomi_status vampomi_dev_kernel_name(const vampomi_ctx* ctx, int which, int K, int mode, char* out, int cap);
 /* The A.x plan for N samples, M markers and `cus` compute units under
  * `variant` (-1 the default, 0-6 the tile plans, 7 the team plan), no device
@@ -390,6 +425,11 @@ vampomi_status vampomi_dev_op_timestamps(vampomi_ctx* ctx, unsigned long long* o
  * buffers and the HIP runtime are not included. */
 vampomi_status vampomi_dev_mem_plan(int64_t N, int64_t Mt, int nranks, int rank, int cus, int probit, int writer,
                                     int64_t* bytes);
+/* vampomi_dev_mem_plan with the storage named (the entry point above means
+ * VAMPOMI_STORE_F64): VAMPOMI_STORE_F32 is smaller by the shard's M*ld*4
+ * bytes.  VAMPOMI_ERR_ARG for any other storage. */
+vampomi_status vampomi_dev_mem_plan_storage(int64_t N, int64_t Mt, int nranks, int rank, int cus, int probit,
+                                            int writer, int storage, int64_t* bytes);
 /* One application of the one-pass CG operator (K <= 2 systems, one rank),
  * host buffers: q_k = ar_k/diag [+ beta_k*qo_k], p_k [= z_k + beta_k*p_k]
  * when z is not null (then qo and beta are required), and

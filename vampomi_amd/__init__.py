@@ -20,11 +20,13 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import (CLI_PATH, GEN_GAUSS, GEN_METH, LIB_PATH, MAX_L, MEM_DEVICE, MEM_HOST, UNIQUE_ID_BYTES,
-                   Params, Result, ShardDesc, Stats, VampomiError, check, load)
+from ._lib import (CLI_PATH, GEN_GAUSS, GEN_METH, LIB_PATH, MAX_L, MEM_DEVICE, MEM_HOST, STORE_F32, STORE_F64,
+                   UNIQUE_ID_BYTES, Params, Result, ShardDesc, Stats, VampomiError, check, load)
 
 __all__ = ["Data", "Vamp", "VampOptions", "divide_work", "comm_unique_id", "VampomiError", "LIB_PATH", "CLI_PATH",
-           "GEN_GAUSS", "GEN_METH", "load"]
+           "GEN_GAUSS", "GEN_METH", "STORE_F64", "STORE_F32", "load"]
+
+_STORAGE = {"f64": STORE_F64, "f32": STORE_F32}
 
 
 def _dp(a: np.ndarray):
@@ -54,10 +56,18 @@ class Data:
     (on-device synthetic); the phenotype with :meth:`read_phen` or
     :meth:`set_phen`.  Marker statistics are computed at load
     (compute_markers_statistics, src/data.cpp:233-283).
+
+    ``storage``: how the shard is held on the device, ``"f64"`` or ``"f32"``
+    (None: the library's default, ``"f64"`` unless ``VAMPOMI_STORAGE`` says
+    otherwise).  With ``"f32"`` the matrix takes half the memory and every pass
+    reads half the bytes; fp64 input is rounded to nearest even at ingest and
+    all arithmetic stays fp64.  The ``storage`` attribute tells which is in use.
     """
 
     def __init__(self, N: int, Mt: int, rank: int = 0, nranks: int = 1, comm_id: Optional[bytes] = None,
-                 device: int = -1, alpha_scale: float = 1.0):
+                 device: int = -1, alpha_scale: float = 1.0, storage: Optional[str] = None):
+        if storage is not None and storage not in _STORAGE:
+            raise ValueError(f'storage must be "f64" or "f32", not {storage!r}')
         self._lib = load()
         self._idbuf = None
         d = ShardDesc(N=N, Mt=Mt, rank=rank, nranks=nranks, device=device, comm_id=None, alpha_scale=alpha_scale)
@@ -73,6 +83,14 @@ class Data:
         M, S, ld = C.c_int64(), C.c_int64(), C.c_int64()
         check(self._lib.vampomi_shard_info(self.ctx, C.byref(M), C.byref(S), C.byref(ld)))
         self.M, self.S, self.ld = M.value, S.value, ld.value
+        if storage is not None:
+            check(self._lib.vampomi_set_storage(self.ctx, _STORAGE[storage]))
+
+    @property
+    def storage(self) -> str:
+        s = C.c_int()
+        check(self._lib.vampomi_get_storage(self.ctx, C.byref(s)))
+        return "f32" if s.value == STORE_F32 else "f64"
 
     # -- lifecycle --
     def close(self):
@@ -99,15 +117,25 @@ class Data:
         check(self._lib.vampomi_barrier(self.ctx))
 
     # -- ingest --
-    def read_methylation_data(self, path: str):
-        check(self._lib.vampomi_load_meth_file(self.ctx, path.encode()))
+    def read_methylation_data(self, path: str, dtype: str = "f64"):
+        """The marker-major file's elements are doubles (``"f64"``) or floats (``"f32"``)."""
+        if dtype not in _STORAGE:
+            raise ValueError(f'dtype must be "f64" or "f32", not {dtype!r}')
+        load_file = self._lib.vampomi_load_meth_file_f32 if dtype == "f32" else self._lib.vampomi_load_meth_file
+        check(load_file(self.ctx, path.encode()))
 
     def load_meth(self, X: np.ndarray):
-        """X: (M, N) float64, this shard's markers (marker-major)."""
-        X = np.ascontiguousarray(X, dtype=np.float64)
+        """X: (M, N), this shard's markers (marker-major): float64, or float32
+        (passed as it is, with no upcast copy, for either storage)."""
+        if getattr(X, "dtype", None) == np.float32:
+            X = np.ascontiguousarray(X)
+            load_host = self._lib.vampomi_load_meth_host_f32
+        else:
+            X = np.ascontiguousarray(X, dtype=np.float64)
+            load_host = self._lib.vampomi_load_meth_host
         if X.shape != (self.M, self.N):
             raise ValueError(f"expected shard shape {(self.M, self.N)}, got {X.shape}")
-        check(self._lib.vampomi_load_meth_host(self.ctx, _dp(X), self.N))
+        check(load_host(self.ctx, _dp(X), self.N))
 
     def generate(self, seed: int, kind: int = GEN_GAUSS):
         check(self._lib.vampomi_generate_meth(self.ctx, seed, kind))

@@ -27,6 +27,7 @@ MAX_L = 64
 UNIQUE_ID_BYTES = 128
 MEM_HOST, MEM_DEVICE = 0, 1
 GEN_GAUSS, GEN_METH = 0, 1
+STORE_F64, STORE_F32 = 0, 1
 
 STATUS = {
     0: "OK", 1: "ERR_ARG", 2: "ERR_HIP", 3: "ERR_RCCL", 4: "ERR_IO",
@@ -105,8 +106,12 @@ SIGNATURES = {
     "vampomi_sync": (C.c_int, [_P]),
     "vampomi_barrier": (C.c_int, [_P]),
     "vampomi_barrier_timeout": (C.c_int, [_P, C.c_double]),
+    "vampomi_set_storage": (C.c_int, [_P, C.c_int]),
+    "vampomi_get_storage": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "vampomi_load_meth_file": (C.c_int, [_P, C.c_char_p]),
+    "vampomi_load_meth_file_f32": (C.c_int, [_P, C.c_char_p]),
     "vampomi_load_meth_host": (C.c_int, [_P, _P, C.c_int64]),
+    "vampomi_load_meth_host_f32": (C.c_int, [_P, _P, C.c_int64]),
     "vampomi_generate_meth": (C.c_int, [_P, C.c_uint64, C.c_int]),
     "vampomi_read_phen": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "vampomi_set_phen": (C.c_int, [_P, _P, C.c_int]),
@@ -143,6 +148,8 @@ SIGNATURES = {
                                            C.POINTER(C.c_int)]),
     "vampomi_dev_kernel_name": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "vampomi_dev_mem_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "vampomi_dev_mem_plan_storage": (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               C.c_int, _P]),
     "vampomi_dev_ax_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_char_p,
                                       C.c_int]),
     "vampomi_dev_op_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_char_p,

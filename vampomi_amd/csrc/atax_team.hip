@@ -219,6 +219,17 @@ __device__ __forceinline__ void tm_publish_l2(unsigned long long* p, const v4u& 
     asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 
+// A row pair of a column tile through its buffer descriptor (nontemporal), as
+// loaded: 16 bytes of a double tile, 8 bytes of a float tile.  A pair past
+// the descriptor's range reads as zero either way
+template <class XE>
+__device__ __forceinline__ xpair_t<XE> tm_ld2(__amdgpu_buffer_rsrc_t rs, int off) {
+    if constexpr (sizeof(XE) == 8)
+        return __builtin_bit_cast(v2d, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 2));
+    else
+        return __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 2));
+}
+
 // KP > 0 (the head-start launch, pcg.cpp): KP plain right-hand sides ride
 // along, z_kp = A x_kp = sum_i (X_i - mave_i) * (msig_i * x_kp[i]) (data::Ax,
 // src/data.cpp:340-373): their coefficients are known when the column is
@@ -270,8 +281,12 @@ __device__ __forceinline__ TmSlots<K> tm_slots(const OpArgs& a, int alt) {
     return s;
 }
 
-template <int K, int S, int F, int L, int P, bool COMM, int E, bool FMA, int KP>
-__device__ __forceinline__ void atax_team_body(const double* __restrict__ X, int64_t ld, int64_t N, int64_t M,
+// XE: X's element type (double, or float for the _f32 entry points).  E counts
+// ROWS per lane per load either way: a float tile is read with loads of half
+// the width (8 bytes for E = 2), its descriptor's range and every byte offset
+// scaled by the element size, and the rows widened as they land.
+template <int K, int S, int F, int L, int P, bool COMM, int E, bool FMA, int KP, class XE>
+__device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t ld, int64_t N, int64_t M,
                                                const double* __restrict__ mave, const double* __restrict__ msig,
                                                const OpArgs& a, int T, int TR, int ilv,
                                                const int* __restrict__ gate) {
@@ -361,7 +376,8 @@ __device__ __forceinline__ void atax_team_body(const double* __restrict__ X, int
     double* s_tot = lds + lay.tot;                        // [2][K] team totals (hand-off)
     const int jb = 64 * E * wave + E * lane;              // row of this lane in step s: RS*s + jb
     // the tile of a column (E = 2: + the zero pad row for odd N)
-    const int nbytes = (E == 2 ? (nrows + 1) & ~1 : nrows) * 8;
+    constexpr int XB = (int)sizeof(XE);
+    const int nbytes = (E == 2 ? (nrows + 1) & ~1 : nrows) * XB;
 
     if (COMM && wave == CW) {
         // ---------------- the hand-off wave ----------------
@@ -612,20 +628,34 @@ __device__ __forceinline__ void atax_team_body(const double* __restrict__ X, int
 #pragma unroll
             for (int e = 0; e < E; ++e) accp[k][s][e] = 0.0;
 
-    double xr[RING][S][E];
+    // A float tile's rows stay in the ring as loaded (xw, half the registers
+    // of xr): dot() and finish() each widen and centre them where they use
+    // them (the same operations on the same values: the same bits as the
+    // centred copy a double tile keeps in xr), so a prefetched column is not
+    // waited for by a conversion and the ring leaves the registers the
+    // conversions need
+    constexpr bool F32 = XB == 4;
+    double xr[F32 ? 1 : RING][S][E];
+    float xw[F32 ? RING : 1][S][E];
     double pk[RING];
     const char* xtile = reinterpret_cast<const char*>(X + mb * ld + r0);
     auto load = [&](int slot, int m) {
         const int64_t c = m * cs;  // offset from mb
         pk[slot] = *tm_chk(pkp + c, pkp - mb, pkp - mb + M, 1024, a.err);  // older than the column's X loads: it lands first
         const __amdgpu_buffer_rsrc_t rs =
-            __builtin_amdgcn_make_buffer_rsrc((void*)(xtile + c * ld * 8), (short)0, nbytes, 0x00020000);
+            __builtin_amdgcn_make_buffer_rsrc((void*)(xtile + c * ld * XB), (short)0, nbytes, 0x00020000);
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-            if constexpr (E == 2) {
-                const v2d x = __builtin_bit_cast(v2d, __builtin_amdgcn_raw_buffer_load_b128(rs, (RS * s + jb) * 8, 0, 2));
+            if constexpr (E == 2 && F32) {
+                const v2f x = tm_ld2<XE>(rs, (RS * s + jb) * XB);
+                xw[slot][s][0] = x.x;
+                xw[slot][s][E - 1] = x.y;
+            } else if constexpr (E == 2) {
+                const v2d x = tm_ld2<XE>(rs, (RS * s + jb) * XB);
                 xr[slot][s][0] = x.x;
                 xr[slot][s][E - 1] = x.y;
+            } else if constexpr (F32) {
+                xw[slot][s][0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (RS * s + jb) * 4, 0, 2));
             } else {
                 xr[slot][s][0] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, (RS * s + jb) * 8, 0, 2));
             }
@@ -652,8 +682,12 @@ __device__ __forceinline__ void atax_team_body(const double* __restrict__ X, int
             double dx[E], q[K][E];
 #pragma unroll
             for (int e = 0; e < E; ++e) {
-                dx[e] = xr[slot][s][e] - me_;
-                xr[slot][s][e] = dx[e];
+                if constexpr (F32) {
+                    dx[e] = (double)xw[slot][s][e] - me_;
+                } else {
+                    dx[e] = xr[slot][s][e] - me_;
+                    xr[slot][s][e] = dx[e];
+                }
             }
             if constexpr (KP > 0) {
 #pragma unroll
@@ -733,17 +767,24 @@ __device__ __forceinline__ void atax_team_body(const double* __restrict__ X, int
                 cc[k] = sg * val;  // Ax: (x - mave) * (msig * x_i)
             }
         }
+        const double mu = F32 ? readlane_d(pk[slot], 0) : 0.0;
 #pragma unroll
         for (int s = 0; s < S; ++s) {
             if (dbg & 8) break;
+            const double me_ = QFULL || valid[s] ? mu : 0.0;  // (a float tile: dot()'s centring again)
 #pragma unroll
             for (int k = 0; k < K; ++k)
 #pragma unroll
-                for (int e = 0; e < E; ++e) {  // xr is centred by dot()
-                    if constexpr (FMA)
-                        acc[k][s][e] = __builtin_fma(xr[slot][s][e], cc[k], acc[k][s][e]);
+                for (int e = 0; e < E; ++e) {
+                    double dx;
+                    if constexpr (F32)
+                        dx = (double)xw[slot][s][e] - me_;
                     else
-                        acc[k][s][e] += xr[slot][s][e] * cc[k];
+                        dx = xr[slot][s][e];  // centred by dot()
+                    if constexpr (FMA)
+                        acc[k][s][e] = __builtin_fma(dx, cc[k], acc[k][s][e]);
+                    else
+                        acc[k][s][e] += dx * cc[k];
                 }
         }
     };
@@ -833,6 +874,15 @@ __global__ __launch_bounds__(kTmThreads) void atax_team_kernel(const double* __r
     atax_team_body<K, S, F, L, P, COMM, E, FMA, 0>(X, ld, N, M, mave, msig, a, T, TR, ilv, gate);
 }
 
+template <int K, int S, int F, int L, int P, bool COMM, int E, bool FMA>
+__global__ __launch_bounds__(kTmThreads) void atax_team_kernel_f32(const float* __restrict__ X, int64_t ld,
+                                                                   int64_t N, int64_t M,
+                                                                   const double* __restrict__ mave,
+                                                                   const double* __restrict__ msig, OpArgs a, int T,
+                                                                   int TR, int ilv, const int* __restrict__ gate) {
+    atax_team_body<K, S, F, L, P, COMM, E, FMA, 0>(X, ld, N, M, mave, msig, a, T, TR, ilv, gate);
+}
+
 // the head-start launch: one operator system (the Onsager solve's first CG
 // step) and kTmPlain plain right-hand sides (pcg.cpp)
 static constexpr int kTmPlain = kOpPlain;
@@ -842,6 +892,16 @@ __global__ __launch_bounds__(kTmThreads) void atax_team_plain_kernel(const doubl
                                                                      const double* __restrict__ mave,
                                                                      const double* __restrict__ msig, OpArgs a, int T,
                                                                      int TR, int ilv, const int* __restrict__ gate) {
+    atax_team_body<1, S, F, L, P, COMM, E, FMA, kTmPlain>(X, ld, N, M, mave, msig, a, T, TR, ilv, gate);
+}
+
+template <int S, int F, int L, int P, bool COMM, int E, bool FMA>
+__global__ __launch_bounds__(kTmThreads) void atax_team_plain_kernel_f32(const float* __restrict__ X, int64_t ld,
+                                                                         int64_t N, int64_t M,
+                                                                         const double* __restrict__ mave,
+                                                                         const double* __restrict__ msig, OpArgs a,
+                                                                         int T, int TR, int ilv,
+                                                                         const int* __restrict__ gate) {
     atax_team_body<1, S, F, L, P, COMM, E, FMA, kTmPlain>(X, ld, N, M, mave, msig, a, T, TR, ilv, gate);
 }
 
@@ -865,13 +925,14 @@ __global__ __launch_bounds__(kTmThreads) void atax_team_plain_kernel(const doubl
 #endif
 static constexpr int kAxTmF = AX_TEAM_F;  // columns prefetched (AX_TEAM_F: experiment builds)
 static constexpr int kAxTmMaxS = 4;    // loads per lane per column (1024-row steps)
-template <int S, int KP, bool FU>
-__global__ __launch_bounds__(kTmThreads) void ax_team_kernel(const double* __restrict__ X, int64_t ld, int64_t N,
-                                                             int64_t M, const double* __restrict__ mave,
-                                                             const double* __restrict__ msig, CPtrs xs,
-                                                             double* __restrict__ part, AxFuse fu, int T, int TR) {
+// (the body of ax_team_kernel and ax_team_kernel_f32: XE is X's element type)
+template <int S, int KP, bool FU, class XE>
+__device__ __forceinline__ void ax_team_body(const XE* __restrict__ X, int64_t ld, int64_t N, int64_t M,
+                                             const double* __restrict__ mave, const double* __restrict__ msig,
+                                             const CPtrs& xs, double* __restrict__ part, const AxFuse& fu, int T,
+                                             int TR) {
     if (fu.gate && !*fu.gate) return;
-    constexpr int E = 2, F = kAxTmF, RING = F + 1;
+    constexpr int E = 2, F = kAxTmF, RING = F + 1, XB = (int)sizeof(XE);
     constexpr int RS = tm_rows_per_step(false, E);  // 1024
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int g = blockIdx.x >> 3;
@@ -881,7 +942,7 @@ __global__ __launch_bounds__(kTmThreads) void ax_team_kernel(const double* __res
     const int n = team < M ? (int)((M - team + nteams - 1) / nteams) : 0;
     const int64_t r0 = (int64_t)member * TR;
     const int nrows = (int)(N - r0 < TR ? N - r0 : TR);  // >= 1 (ax_team_plan)
-    const int nbytes = ((nrows + 1) & ~1) * 8;            // the tile (+ the zero pad row for odd N)
+    const int nbytes = ((nrows + 1) & ~1) * XB;           // the tile (+ the zero pad row for odd N)
     const int jb = 64 * E * wave + E * lane;              // row of this lane in step s: RS*s + jb
     double bk[KP];
 #pragma unroll
@@ -902,19 +963,17 @@ __global__ __launch_bounds__(kTmThreads) void ax_team_kernel(const double* __res
         for (int s = 0; s < S; ++s)
 #pragma unroll
             for (int e = 0; e < E; ++e) acc[k][s][e] = 0.0;
-    double xr[RING][S][E];
+    xpair_t<XE> xr[RING][S];  // as loaded (widened where it is used)
     double pk[RING];
     const char* xtile = reinterpret_cast<const char*>(X + (int64_t)team * ld + r0);
     auto load = [&](int slot, int m) {
         const int64_t c = (int64_t)m * nteams;
         pk[slot] = pkp[c];  // older than the column's X loads: it lands first
         const __amdgpu_buffer_rsrc_t rs =
-            __builtin_amdgcn_make_buffer_rsrc((void*)(xtile + c * ld * 8), (short)0, nbytes, 0x00020000);
+            __builtin_amdgcn_make_buffer_rsrc((void*)(xtile + c * ld * XB), (short)0, nbytes, 0x00020000);
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-            const v2d x = __builtin_bit_cast(v2d, __builtin_amdgcn_raw_buffer_load_b128(rs, (RS * s + jb) * 8, 0, 2));
-            xr[slot][s][0] = x.x;
-            xr[slot][s][1] = x.y;
+            xr[slot][s] = tm_ld2<XE>(rs, (RS * s + jb) * XB);
         }
     };
     if (n > 0) {
@@ -940,7 +999,7 @@ __global__ __launch_bounds__(kTmThreads) void ax_team_kernel(const double* __res
                     for (int s = 0; s < S; ++s)
 #pragma unroll
                         for (int e = 0; e < E; ++e) {
-                            const double dx = xr[i][s][e] - mu;  // rows past the tile: never stored
+                            const double dx = widen(xr[i][s])[e] - mu;  // rows past the tile: never stored
 #pragma unroll
                             for (int k = 0; k < KP; ++k) {
                                 if constexpr (TM_FMA)
@@ -969,6 +1028,23 @@ __global__ __launch_bounds__(kTmThreads) void ax_team_kernel(const double* __res
             for (int e = 0; e < E; ++e)
                 if (jl + e < nrows) dst[(int64_t)k * ld + jl + e] = acc[k][s][e];
     }
+}
+
+template <int S, int KP, bool FU>
+__global__ __launch_bounds__(kTmThreads) void ax_team_kernel(const double* __restrict__ X, int64_t ld, int64_t N,
+                                                             int64_t M, const double* __restrict__ mave,
+                                                             const double* __restrict__ msig, CPtrs xs,
+                                                             double* __restrict__ part, AxFuse fu, int T, int TR) {
+    ax_team_body<S, KP, FU>(X, ld, N, M, mave, msig, xs, part, fu, T, TR);
+}
+
+template <int S, int KP, bool FU>
+__global__ __launch_bounds__(kTmThreads) void ax_team_kernel_f32(const float* __restrict__ X, int64_t ld, int64_t N,
+                                                                 int64_t M, const double* __restrict__ mave,
+                                                                 const double* __restrict__ msig, CPtrs xs,
+                                                                 double* __restrict__ part, AxFuse fu, int T,
+                                                                 int TR) {
+    ax_team_body<S, KP, FU>(X, ld, N, M, mave, msig, xs, part, fu, T, TR);
 }
 
 // ---------------------------------------------------------------------------
@@ -1026,15 +1102,21 @@ bool team_lds_layout(const OpPlan& pl, int64_t N, int K, int64_t out[6]) {
 // occ != null: no launch, *occ = the workgroups of this instantiation one CU
 // holds at once (hipOccupancyMaxActiveBlocksPerMultiprocessor).  PL: the
 // head-start kernel (K = 1 operator system + kTmPlain plain right-hand sides)
-template <int K, int S, int C, bool PL>
-static hipError_t launch_tm(const Shard& s, const OpPlan& pl, const OpArgs& a, hipStream_t st, const Timing& tm,
-                            const int* gate, int* occ) {
+// XE: the shard's element type (the _f32 entry points for float)
+template <int K, int S, int C, bool PL, class XE>
+static hipError_t launch_tm_e(const Shard& s, const OpPlan& pl, const OpArgs& a, hipStream_t st, const Timing& tm,
+                              const int* gate, int* occ) {
     constexpr TmCfg c = kTmCfg[C];
     static_assert(!PL || K == 1, "the head-start kernel has one operator system");
-    void (*kern)(const double*, int64_t, int64_t, int64_t, const double*, const double*, OpArgs, int, int, int,
+    constexpr bool F32 = sizeof(XE) == 4;
+    void (*kern)(const XE*, int64_t, int64_t, int64_t, const double*, const double*, OpArgs, int, int, int,
                  const int*);
-    if constexpr (PL)
+    if constexpr (PL && F32)
+        kern = atax_team_plain_kernel_f32<S, c.F, c.L, c.P, c.comm, c.E, (bool)TM_FMA>;
+    else if constexpr (PL)
         kern = atax_team_plain_kernel<S, c.F, c.L, c.P, c.comm, c.E, (bool)TM_FMA>;
+    else if constexpr (F32)
+        kern = atax_team_kernel_f32<K, S, c.F, c.L, c.P, c.comm, c.E, (bool)TM_FMA>;
     else
         kern = atax_team_kernel<K, S, c.F, c.L, c.P, c.comm, c.E, (bool)TM_FMA>;
     const size_t lds = (size_t)tm_lds(K, S, c.comm, c.E, std::min<int64_t>(pl.TR, s.N)).words * sizeof(double);
@@ -1048,9 +1130,17 @@ static hipError_t launch_tm(const Shard& s, const OpPlan& pl, const OpArgs& a, h
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, kern, kTmThreads, lds) != hipSuccess) *occ = 0;
         return hipSuccess;
     }
-    hipExtLaunchKernelGGL(kern, dim3(pl.grid), dim3(kTmThreads), lds, st, tm.start, tm.stop, 0, s.X, s.ld, s.N, s.M,
-                          s.mave, s.msig, a, pl.T, pl.TR, c.ilv ? 1 : 0, gate);
+    hipExtLaunchKernelGGL(kern, dim3(pl.grid), dim3(kTmThreads), lds, st, tm.start, tm.stop, 0,
+                          static_cast<const XE*>(s.X), s.ld, s.N, s.M, s.mave, s.msig, a, pl.T, pl.TR, c.ilv ? 1 : 0,
+                          gate);
     return hipSuccess;
+}
+
+template <int K, int S, int C, bool PL>
+static hipError_t launch_tm(const Shard& s, const OpPlan& pl, const OpArgs& a, hipStream_t st, const Timing& tm,
+                            const int* gate, int* occ) {
+    if (s.f32) return launch_tm_e<K, S, C, PL, float>(s, pl, a, st, tm, gate, occ);
+    return launch_tm_e<K, S, C, PL, double>(s, pl, a, st, tm, gate, occ);
 }
 
 // the most loads per lane per column the head-start kernel is instantiated
@@ -1179,8 +1269,12 @@ bool ax_team_plan(int64_t N, int64_t M, int cus, AxPlan* out) {
 template <int S, int K, bool FU>
 static void launch_axt(const Shard& s, const AxPlan& pl, CPtrs x, double* part, hipStream_t st, const Timing& tm,
                        const AxFuse& fu) {
-    hipExtLaunchKernelGGL((ax_team_kernel<S, K, FU>), dim3(pl.groups), dim3(kTmThreads), 0, st, tm.start, tm.stop, 0,
-                          s.X, s.ld, s.N, s.M, s.mave, s.msig, x, part, fu, pl.T, pl.TR);
+    if (s.f32)
+        hipExtLaunchKernelGGL((ax_team_kernel_f32<S, K, FU>), dim3(pl.groups), dim3(kTmThreads), 0, st, tm.start,
+                              tm.stop, 0, s.x32(), s.ld, s.N, s.M, s.mave, s.msig, x, part, fu, pl.T, pl.TR);
+    else
+        hipExtLaunchKernelGGL((ax_team_kernel<S, K, FU>), dim3(pl.groups), dim3(kTmThreads), 0, st, tm.start,
+                              tm.stop, 0, s.x64(), s.ld, s.N, s.M, s.mave, s.msig, x, part, fu, pl.T, pl.TR);
 }
 
 template <int S>
@@ -1221,10 +1315,10 @@ hipError_t ax_team(const Shard& s, const AxPlan& pl, int K, CPtrs x, double* par
     return hipGetLastError();
 }
 
-std::string ax_kernel_name(int K, bool fused, const AxPlan& pl) {
-    if (pl.T <= 0) return kernel_name(0, K, fused ? 1 : 0, pl.variant);
+std::string ax_kernel_name(int K, bool fused, const AxPlan& pl, int f32) {
+    if (pl.T <= 0) return kernel_name(0, K, fused ? 1 : 0, pl.variant, f32);
     char b[96];
-    std::snprintf(b, sizeof b, "ax_team_kernel<%d, %d, %s>", pl.S, K, fused ? "true" : "false");
+    std::snprintf(b, sizeof b, "ax_team_kernel%s<%d, %d, %s>", f32 ? "_f32" : "", pl.S, K, fused ? "true" : "false");
     return b;
 }
 
@@ -1246,9 +1340,9 @@ bool team_plain_plan(int64_t N, int64_t M, int cus, const OpPlan& main, OpPlan* 
     return false;
 }
 
-int team_occupancy(const OpPlan& pl, int K) {
+int team_occupancy(const OpPlan& pl, int K, int f32) {
     int occ = 0;
-    const Shard s{nullptr, 0, (int64_t)pl.TR * pl.T, 1, nullptr, nullptr};  // the LDS size needs TR and N only
+    const Shard s{nullptr, 0, (int64_t)pl.TR * pl.T, 1, nullptr, nullptr, f32};  // the LDS size needs TR and N only
     const OpArgs a{};
     hipError_t e = hipErrorInvalidValue;
     switch (K) {
@@ -1260,14 +1354,15 @@ int team_occupancy(const OpPlan& pl, int K) {
     return e == hipSuccess ? occ : 0;
 }
 
-std::string team_kernel_name(int K, const OpPlan& pl) {
+std::string team_kernel_name(int K, const OpPlan& pl, int f32) {
     const TmCfg& c = kTmCfg[pl.cfg];
+    const char* sfx = f32 ? "_f32" : "";
     char b[128];
     if (K == 1 + kTmPlain)  // the head-start kernel
-        std::snprintf(b, sizeof b, "atax_team_plain_kernel<%d, %d, %d, %d, %s, %d>", pl.S, c.F, c.L, c.P,
+        std::snprintf(b, sizeof b, "atax_team_plain_kernel%s<%d, %d, %d, %d, %s, %d>", sfx, pl.S, c.F, c.L, c.P,
                       c.comm ? "true" : "false", c.E);
     else
-        std::snprintf(b, sizeof b, "atax_team_kernel<%d, %d, %d, %d, %d, %s, %d>", K, pl.S, c.F, c.L, c.P,
+        std::snprintf(b, sizeof b, "atax_team_kernel%s<%d, %d, %d, %d, %d, %s, %d>", sfx, K, pl.S, c.F, c.L, c.P,
                       c.comm ? "true" : "false", c.E);
     return b;
 }

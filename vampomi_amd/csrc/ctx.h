@@ -91,7 +91,11 @@ struct vampomi_ctx {
     uint64_t coll_seq = 0;  // collectives issued so far (divergence checks)
     bool aborted = false;   // comm_abort ran: no further collective
 
-    double* X = nullptr;     // M columns x ld, marker-major, pad rows zero
+    // M columns x ld, marker-major, pad rows zero: doubles, or floats with
+    // storage == VAMPOMI_STORE_F32 (fixed once X is allocated; rank-local: the
+    // ranks agree on nothing that depends on it)
+    void* X = nullptr;
+    int storage = VAMPOMI_STORE_F64;
     double* mave = nullptr;
     double* msig = nullptr;
     double* y = nullptr;     // ld, zero pad
@@ -158,7 +162,9 @@ struct vampomi_ctx {
     std::unique_ptr<VampRun> run;
     std::unique_ptr<IterWriter> writer;  // per-iteration output (writer.h), created with the context
 
-    vk::Shard shard() const { return vk::Shard{X, ld, N, M, mave, msig}; }
+    bool f32() const { return storage == VAMPOMI_STORE_F32; }
+    int64_t esize() const { return f32() ? 4 : 8; }  // bytes per element of X
+    vk::Shard shard() const { return vk::Shard{X, ld, N, M, mave, msig, f32() ? 1 : 0}; }
     vampomi_ctx();   // defined in vamp.cpp, where VampRun is complete
     ~vampomi_ctx();
 };
@@ -382,7 +388,7 @@ vampomi_status op_agree(vampomi_ctx* c);
 // whether pcg_run's head start can run on this context (plans the operator;
 // the same answer on every rank)
 vampomi_status headstart_available(vampomi_ctx* c, bool* yes);
-// the smallest X shard at which the auto pre-step turns on (bytes; never below
+// the smallest X shard at which the auto pre-step turns on (its bytes as stored; never below
 // 256 MiB: the pinned default schedules of the small test shapes stay)
 constexpr int64_t kPreMinBytes = (int64_t)256 << 20;
 // whether the linear model's solves use the pre-step on this context (where

@@ -79,10 +79,11 @@ static hipEvent_t ev_get(vampomi_ctx* c) {
 }
 
 // algorithmic bytes / flops of one pass with K right-hand sides:
-// X once, the K N-vectors, mave/msig and the K M-vectors; (x - mu) once per
-// element and one fma per right-hand side.
+// X once (at its stored element size), the K N-vectors, mave/msig and the K
+// M-vectors; (x - mu) once per element and one fma per right-hand side.
 static double pass_bytes(const vampomi_ctx* c, int K) {
-    return 8.0 * (double)c->N * (double)c->M + 8.0 * K * (double)c->N + 8.0 * (2.0 + K) * (double)c->M;
+    return (double)c->esize() * (double)c->N * (double)c->M + 8.0 * K * (double)c->N +
+           8.0 * (2.0 + K) * (double)c->M;
 }
 static double pass_flops(const vampomi_ctx* c, int K) { return (double)c->N * (double)c->M * (1.0 + 2.0 * K); }
 
@@ -813,11 +814,11 @@ static vampomi_status op_plan_local(vampomi_ctx* c) {
         // K; a device that cannot (or an occupancy query that failed) runs the
         // CG on the two-pass schedule instead
         for (int K = 1; K <= vk::kOpMaxK && op_ok; ++K) {
-            const int occ = vk::team_occupancy(c->opp, K);
+            const int occ = vk::team_occupancy(c->opp, K, c->f32());
             if ((int64_t)occ * c->cus < c->opp.grid) {
                 std::fprintf(stderr, "libvampomi: one-pass operator off: %s fits %d workgroup(s) per CU; the plan "
                                      "needs %lld resident on %d CUs (two passes per CG step)\n",
-                             vk::team_kernel_name(K, c->opp).c_str(), occ, (long long)c->opp.grid, c->cus);
+                             vk::team_kernel_name(K, c->opp, c->f32()).c_str(), occ, (long long)c->opp.grid, c->cus);
                 op_ok = false;
             }
         }
@@ -825,7 +826,7 @@ static vampomi_status op_plan_local(vampomi_ctx* c) {
     // the head-start plan: optional (no plan, or a grid the device cannot
     // hold, only means the solves start without it)
     bool hs_ok = op_ok && vk::team_plain_plan(c->N, M, c->cus, c->opp, &c->opp_hs);
-    if (hs_ok && (int64_t)vk::team_occupancy(c->opp_hs, 1 + vk::kOpPlain) * c->cus < c->opp_hs.grid) hs_ok = false;
+    if (hs_ok && (int64_t)vk::team_occupancy(c->opp_hs, 1 + vk::kOpPlain, c->f32()) * c->cus < c->opp_hs.grid) hs_ok = false;
     c->op_ok_mine = op_ok;
     c->hs_ok_mine = hs_ok;
     if (!c->op_ts && std::getenv("VAMPOMI_OP_TS") && std::atoi(std::getenv("VAMPOMI_OP_TS"))) {
@@ -1124,7 +1125,9 @@ void release_ctx_resources(vampomi_ctx* c) {
     resolve_timing(c);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     c->ev_pool.clear();
-    for (double** p : {&c->X, &c->mave, &c->msig, &c->y, &c->ax_part, &c->red_part, &c->scal, &c->nbuf, &c->mbuf,
+    if (c->X) (void)hipFree(c->X);
+    c->X = nullptr;
+    for (double** p : {&c->mave, &c->msig, &c->y, &c->ax_part, &c->red_part, &c->scal, &c->nbuf, &c->mbuf,
                        &c->op_part, &c->op_nvec})
         dev_free(*p);
     if (c->op_xg) (void)hipFree(c->op_xg);
@@ -1168,7 +1171,15 @@ extern "C" vampomi_status vampomi_open(const vampomi_shard_desc* d, vampomi_ctx*
         return fail(VAMPOMI_ERR_ARG, "invalid shard description (N >= 2, Mt >= 1, 0 <= rank < nranks)");
     if (d->nranks > 1 && !d->comm_id) return fail(VAMPOMI_ERR_ARG, "nranks > 1 needs a communicator id");
     if (d->Mt < d->nranks) return fail(VAMPOMI_ERR_ARG, "every rank needs at least one marker (Mt >= nranks)");
+    int storage = VAMPOMI_STORE_F64;
+    if (const char* sv = std::getenv("VAMPOMI_STORAGE")) {  // the default storage (vampomi_set_storage)
+        if (std::strcmp(sv, "f32") == 0)
+            storage = VAMPOMI_STORE_F32;
+        else if (std::strcmp(sv, "f64") != 0)
+            return fail(VAMPOMI_ERR_ARG, std::string("VAMPOMI_STORAGE must be f32 or f64, not '") + sv + "'");
+    }
     std::unique_ptr<vampomi_ctx> c(new vampomi_ctx());
+    c->storage = storage;
     c->rank = d->rank;
     c->nranks = d->nranks;
     c->N = d->N;
@@ -1289,27 +1300,108 @@ extern "C" vampomi_status vampomi_barrier_timeout(vampomi_ctx* c, double seconds
 // ---------------------------------------------------------------------------
 static vampomi_status ensure_X(vampomi_ctx* c) {
     if (c->X) return VAMPOMI_OK;
-    return dev_alloc(&c->X, (size_t)std::max<int64_t>(c->M, 1) * (size_t)c->ld);
+    const size_t bytes = (size_t)std::max<int64_t>(c->M, 1) * (size_t)c->ld * (size_t)c->esize();
+    const hipError_t e = hipMalloc(&c->X, bytes);
+    if (e != hipSuccess)
+        return fail(VAMPOMI_ERR_OOM, "hipMalloc(" + std::to_string(bytes) + " B): " + hipGetErrorString(e));
+    return VAMPOMI_OK;
+}
+
+extern "C" vampomi_status vampomi_set_storage(vampomi_ctx* c, int storage) {
+    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
+    if (storage != VAMPOMI_STORE_F64 && storage != VAMPOMI_STORE_F32)
+        return fail(VAMPOMI_ERR_ARG, "storage must be VAMPOMI_STORE_F64 or VAMPOMI_STORE_F32");
+    if (c->X) return fail(VAMPOMI_ERR_STATE, "the storage is fixed once the methylation shard is allocated");
+    c->storage = storage;
+    return VAMPOMI_OK;
+}
+
+extern "C" vampomi_status vampomi_get_storage(const vampomi_ctx* c, int* storage) {
+    if (!c || !storage) return fail(VAMPOMI_ERR_ARG, "null argument");
+    *storage = c->storage;
+    return VAMPOMI_OK;
 }
 
 static vampomi_status finish_X(vampomi_ctx* c) {
+    const size_t es = (size_t)c->esize();
     if (c->ld > c->N && c->M > 0)
-        HIPCHK(hipMemset2DAsync(c->X + c->N, (size_t)c->ld * 8, 0, (size_t)(c->ld - c->N) * 8, (size_t)c->M, c->st));
+        HIPCHK(hipMemset2DAsync((char*)c->X + (size_t)c->N * es, (size_t)c->ld * es, 0, (size_t)(c->ld - c->N) * es,
+                                (size_t)c->M, c->st));
     // compute_markers_statistics with nonas = N (read_phen asserts N rows, src/data.cpp:85)
-    HIPCHK(vk::marker_stats(c->X, c->ld, c->N, c->M, (double)c->N, c->alpha_scale, c->mave, c->msig, c->st));
+    HIPCHK(vk::marker_stats(c->shard(), (double)c->N, c->alpha_scale, c->mave, c->msig, c->st));
     STCHK(sync_stream(c, c->st));
     c->have_X = true;
     return VAMPOMI_OK;
 }
 
-extern "C" vampomi_status vampomi_load_meth_host(vampomi_ctx* c, const double* X, int64_t ld_in) {
+// Columns [i0, i0 + nc) of the shard from a host block of nc columns of
+// elements of in_es bytes (8: doubles, 4: floats), column stride ld_in
+// elements.  The same element type as the storage: a strided copy into the
+// padded layout.  Otherwise the block is staged on the device as it is and
+// converted there (vk::narrow_cols, nearest even / vk::widen_cols, exact):
+// *stage (cap_bytes; grown as needed, freed by the caller) is that buffer.  All
+// on the context's stream, so the caller may reuse src once the stream has
+// passed this point.
+static vampomi_status put_cols(vampomi_ctx* c, int64_t i0, int64_t nc, const void* src, int64_t ld_in, int in_es,
+                               void** stage, size_t* cap_bytes) {
+    if (nc <= 0) return VAMPOMI_OK;
+    const size_t es = (size_t)c->esize();
+    char* dst = (char*)c->X + (size_t)i0 * (size_t)c->ld * es;
+    if ((size_t)in_es == es) {
+        HIPCHK(hipMemcpy2DAsync(dst, (size_t)c->ld * es, src, (size_t)ld_in * es, (size_t)c->N * es, (size_t)nc,
+                                hipMemcpyHostToDevice, c->st));
+        return VAMPOMI_OK;
+    }
+    const size_t need = (size_t)nc * (size_t)c->N * (size_t)in_es;
+    if (*cap_bytes < need) {
+        HIPCHK(hipStreamSynchronize(c->st));
+        if (*stage) (void)hipFree(*stage);
+        *stage = nullptr;
+        *cap_bytes = 0;
+        if (hipMalloc(stage, need) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(VAMPOMI_ERR_OOM, "device staging buffer of the storage conversion");
+        }
+        *cap_bytes = need;
+    }
+    HIPCHK(hipMemcpy2DAsync(*stage, (size_t)c->N * in_es, src, (size_t)ld_in * in_es, (size_t)c->N * in_es,
+                            (size_t)nc, hipMemcpyHostToDevice, c->st));
+    if (in_es == 8)
+        HIPCHK(vk::narrow_cols((const double*)*stage, c->N, c->N, nc, (float*)dst, c->ld, c->st));
+    else
+        HIPCHK(vk::widen_cols((const float*)*stage, c->N, c->N, nc, (double*)dst, c->ld, c->st));
+    return VAMPOMI_OK;
+}
+
+// a host shard of doubles (in_es 8) or floats (4), in chunks of about 256 MB
+// where it has to be converted (put_cols' staging buffer)
+static vampomi_status load_host(vampomi_ctx* c, const void* X, int64_t ld_in, int in_es) {
     if (!c || (!X && c->M > 0) || ld_in < c->N) return fail(VAMPOMI_ERR_ARG, "invalid host shard");
     HIPCHK(hipSetDevice(c->device));
     STCHK(ensure_X(c));
-    if (c->M > 0)
-        HIPCHK(hipMemcpy2DAsync(c->X, (size_t)c->ld * 8, X, (size_t)ld_in * 8, (size_t)c->N * 8, (size_t)c->M,
-                                hipMemcpyHostToDevice, c->st));
+    void* stage = nullptr;
+    size_t cap = 0;
+    vampomi_status st = VAMPOMI_OK;
+    const int64_t chunk = (int64_t)in_es == c->esize()
+                              ? std::max<int64_t>(c->M, 1)
+                              : std::max<int64_t>(1, ((int64_t)256 << 20) / (c->N * in_es));
+    for (int64_t i0 = 0; i0 < c->M && st == VAMPOMI_OK; i0 += chunk)
+        st = put_cols(c, i0, std::min(chunk, c->M - i0), (const char*)X + (size_t)i0 * (size_t)ld_in * in_es, ld_in,
+                      in_es, &stage, &cap);
+    if (stage) {
+        (void)hipStreamSynchronize(c->st);
+        (void)hipFree(stage);
+    }
+    if (st != VAMPOMI_OK) return st;
     return finish_X(c);
+}
+
+extern "C" vampomi_status vampomi_load_meth_host(vampomi_ctx* c, const double* X, int64_t ld_in) {
+    return load_host(c, X, ld_in, 8);
+}
+
+extern "C" vampomi_status vampomi_load_meth_host_f32(vampomi_ctx* c, const float* X, int64_t ld_in) {
+    return load_host(c, X, ld_in, 4);
 }
 
 // [off, off + want) of fd into dst, split over nt reader threads (page cache
@@ -1339,24 +1431,30 @@ static bool pread_parallel(int fd, char* dst, size_t want, off_t off, int nt) {
     return ok;
 }
 
-// read_methylation_data (src/data.cpp:116-153): this rank's M*N doubles at byte
-// offset S*N*8 (64-bit offsets: the reference's int i*N overflows past 2^31
-// elements), streamed through three pinned 256 MB staging buffers: the
-// parallel read of chunk k+1 overlaps the host-to-device copy of chunk k,
-// which lands directly in the ld-padded column layout.  Marker statistics
-// follow on the device (finish_X).
-extern "C" vampomi_status vampomi_load_meth_file(vampomi_ctx* c, const char* path) {
+// read_methylation_data (src/data.cpp:116-153): this rank's M*N elements of
+// in_es bytes (8: the reference's doubles; 4: floats in the same marker-major
+// layout) at byte offset S*N*in_es (64-bit offsets: the reference's int i*N
+// overflows past 2^31 elements), streamed through three pinned 256 MB staging
+// buffers: the parallel read of chunk k+1 overlaps the host-to-device copy of
+// chunk k, which lands directly in the ld-padded column layout, or, where the
+// file's element type is not the storage's, in a device staging buffer that a
+// conversion kernel empties into it (put_cols).  Marker statistics follow on
+// the device (finish_X).
+static vampomi_status load_file(vampomi_ctx* c, const char* path, int in_es) {
     if (!c || !path) return fail(VAMPOMI_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(c->device));
     int fd = ::open(path, O_RDONLY);
     if (fd < 0) return fail(VAMPOMI_ERR_IO, std::string("cannot open methylation file ") + path);
-    STCHK(ensure_X(c));
-    const size_t colb = (size_t)c->N * 8;
+    if (const vampomi_status s0 = ensure_X(c)) {
+        ::close(fd);
+        return s0;
+    }
+    const size_t colb = (size_t)c->N * (size_t)in_es;
     const size_t chunk_cols = std::max<size_t>(1, ((size_t)256 << 20) / colb);
     const char* env = std::getenv("VAMPOMI_IO_THREADS");
     const int nt = env ? std::max(1, std::atoi(env)) : (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
     constexpr int NB = 3;
-    double* pin[NB] = {};
+    char* pin[NB] = {};
     hipEvent_t done[NB];
     bool used[NB] = {};
     for (int b = 0; b < NB; ++b) {
@@ -1367,6 +1465,8 @@ extern "C" vampomi_status vampomi_load_meth_file(vampomi_ctx* c, const char* pat
         }
         (void)hipEventCreate(&done[b]);
     }
+    void* stage = nullptr;  // put_cols' device staging buffer (conversions only)
+    size_t stage_cap = 0;
     vampomi_status st = VAMPOMI_OK;
     int64_t i0 = 0;
     int b = 0;
@@ -1375,13 +1475,13 @@ extern "C" vampomi_status vampomi_load_meth_file(vampomi_ctx* c, const char* pat
         if (used[b]) (void)hipEventSynchronize(done[b]);
         const size_t want = (size_t)nc * colb;
         const off_t off = (off_t)(c->S + i0) * (off_t)colb;
-        if (!pread_parallel(fd, (char*)pin[b], want, off, nt)) {
+        if (!pread_parallel(fd, pin[b], want, off, nt)) {
             st = fail(VAMPOMI_ERR_IO, std::string("short read from methylation file ") + path);
             break;
         }
-        if (hipMemcpy2DAsync(c->X + i0 * c->ld, (size_t)c->ld * 8, pin[b], colb, colb, (size_t)nc, hipMemcpyHostToDevice,
-                             c->st) != hipSuccess ||
-            hipEventRecord(done[b], c->st) != hipSuccess) {
+        st = put_cols(c, i0, nc, pin[b], c->N, in_es, &stage, &stage_cap);
+        if (st != VAMPOMI_OK) break;
+        if (hipEventRecord(done[b], c->st) != hipSuccess) {
             st = fail(VAMPOMI_ERR_HIP, "host-to-device copy of the methylation shard");
             break;
         }
@@ -1394,16 +1494,23 @@ extern "C" vampomi_status vampomi_load_meth_file(vampomi_ctx* c, const char* pat
         (void)hipHostFree(pin[k]);
         (void)hipEventDestroy(done[k]);
     }
+    if (stage) (void)hipFree(stage);
     ::close(fd);
     if (st != VAMPOMI_OK) return st;
     return finish_X(c);
+}
+
+extern "C" vampomi_status vampomi_load_meth_file(vampomi_ctx* c, const char* path) { return load_file(c, path, 8); }
+
+extern "C" vampomi_status vampomi_load_meth_file_f32(vampomi_ctx* c, const char* path) {
+    return load_file(c, path, 4);
 }
 
 extern "C" vampomi_status vampomi_generate_meth(vampomi_ctx* c, uint64_t seed, int kind) {
     if (!c || (kind != VAMPOMI_GEN_GAUSS && kind != VAMPOMI_GEN_METH)) return fail(VAMPOMI_ERR_ARG, "bad argument");
     HIPCHK(hipSetDevice(c->device));
     STCHK(ensure_X(c));
-    HIPCHK(vk::gen_markers(seed, kind, c->N, c->ld, c->S, c->M, c->X, c->st));
+    HIPCHK(vk::gen_markers(seed, kind, c->N, c->ld, c->S, c->M, c->X, c->f32() ? 1 : 0, c->st));
     return finish_X(c);
 }
 
@@ -1457,11 +1564,31 @@ extern "C" vampomi_status vampomi_read_markers(vampomi_ctx* c, int64_t i0, int64
     if (!c || !out || i0 < 0 || count < 0 || i0 + count > c->M) return fail(VAMPOMI_ERR_ARG, "bad marker range");
     if (!c->have_X) return fail(VAMPOMI_ERR_STATE, "no methylation data loaded");
     HIPCHK(hipSetDevice(c->device));
-    if (count > 0)
-        HIPCHK(hipMemcpy2DAsync(out, (size_t)c->N * 8, c->X + i0 * c->ld, (size_t)c->ld * 8, (size_t)c->N * 8,
-                                (size_t)count, hipMemcpyDeviceToHost, c->st));
-    STCHK(sync_stream(c, c->st));
-    return VAMPOMI_OK;
+    if (count > 0 && !c->f32())
+        HIPCHK(hipMemcpy2DAsync(out, (size_t)c->N * 8, (const double*)c->X + i0 * c->ld, (size_t)c->ld * 8,
+                                (size_t)c->N * 8, (size_t)count, hipMemcpyDeviceToHost, c->st));
+    // fp32 storage: the stored floats widened on the device (exact), in chunks
+    // of about 64 MB through a staging buffer
+    void* stage = nullptr;
+    if (count > 0 && c->f32()) {
+        const int64_t chunk = std::min<int64_t>(count, std::max<int64_t>(1, ((int64_t)64 << 20) / (c->N * 8)));
+        HIPCHK(hipMalloc(&stage, (size_t)chunk * (size_t)c->N * 8));
+        for (int64_t k = 0; k < count; k += chunk) {
+            const int64_t nc = std::min(chunk, count - k);
+            hipError_t e = vk::widen_cols((const float*)c->X + (i0 + k) * c->ld, c->ld, c->N, nc, (double*)stage,
+                                          c->N, c->st);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(out + k * c->N, stage, (size_t)nc * (size_t)c->N * 8, hipMemcpyDeviceToHost, c->st);
+            if (e != hipSuccess) {
+                (void)hipStreamSynchronize(c->st);
+                (void)hipFree(stage);
+                return fail(VAMPOMI_ERR_HIP, std::string("read_markers: ") + hipGetErrorString(e));
+            }
+        }
+    }
+    const vampomi_status st = sync_stream(c, c->st);
+    if (stage) (void)hipFree(stage);
+    return st;
 }
 
 extern "C" vampomi_status vampomi_simulate_phen(vampomi_ctx* c, uint64_t seed, double lam, double h2, double* beta_out) {
@@ -1699,7 +1826,8 @@ extern "C" vampomi_status vampomi_assoc_loo(vampomi_ctx* c, const double* est, d
     if (ld > N) HIPCHK(hipMemsetAsync(ymod + N, 0, (size_t)(ld - N) * 8, c->st));
     // raw X once, ymod, x1, the five sums; per element 1 div, 2 mul + 1 add
     // for ym, 5 accumulations (3 of them products)
-    TimedLaunch t = launch_stat(c, 2, 1, 8.0 * (double)N * (double)M + 8.0 * (double)N + 8.0 * 6.0 * (double)M,
+    TimedLaunch t = launch_stat(c, 2, 1,
+                                (double)c->esize() * (double)N * (double)M + 8.0 * (double)N + 8.0 * 6.0 * (double)M,
                                 11.0 * (double)N * (double)M);
     HIPCHK(vk::loo_sums(c->shard(), ymod, x1, std::sqrt((double)N), st, c->st, c->loo_variant, vk::Timing{t.a, t.b}));  // :393-416
     c->stats.a_passes_exec++;
@@ -1847,7 +1975,7 @@ extern "C" vampomi_status vampomi_dev_set_variant(vampomi_ctx* c, int which, int
 
 bool prestep_on(const vampomi_ctx* c) {
     if (c->use_comm || c->nranks != 1 || !c->hs_ok || c->pre_mode == 0) return false;
-    return c->pre_mode == 1 || std::max<int64_t>(c->M, 1) * c->ld * 8 >= kPreMinBytes;
+    return c->pre_mode == 1 || std::max<int64_t>(c->M, 1) * c->ld * c->esize() >= kPreMinBytes;
 }
 
 extern "C" vampomi_status vampomi_dev_prestep_counts(const vampomi_ctx* c, int64_t* made, int64_t* used) {
@@ -2022,9 +2150,10 @@ extern "C" vampomi_status vampomi_dev_op_lds(int64_t N, int64_t M, int cus, int 
 // batch_rhs 4), vamp_alloc / probit_begin and the iteration writer allocate,
 // summed (each hipMalloc rounded up to 2 MiB, the allocator's granularity for
 // large blocks).  RCCL's own buffers and the HIP runtime are not included.
-extern "C" vampomi_status vampomi_dev_mem_plan(int64_t N, int64_t Mt, int nranks, int rank, int cus, int probit,
-                                               int writer, int64_t* bytes) {
-    if (!bytes || N < 2 || Mt < nranks || nranks < 1 || rank < 0 || rank >= nranks || cus < 1)
+extern "C" vampomi_status vampomi_dev_mem_plan_storage(int64_t N, int64_t Mt, int nranks, int rank, int cus,
+                                                       int probit, int writer, int storage, int64_t* bytes) {
+    if (!bytes || N < 2 || Mt < nranks || nranks < 1 || rank < 0 || rank >= nranks || cus < 1 ||
+        (storage != VAMPOMI_STORE_F64 && storage != VAMPOMI_STORE_F32))
         return fail(VAMPOMI_ERR_ARG, "bad argument");
     int64_t M = 0, S = 0, Mm = 0;
     vampomi_divide_work(Mt, nranks, rank, &M, &S, &Mm);
@@ -2035,7 +2164,7 @@ extern "C" vampomi_status vampomi_dev_mem_plan(int64_t N, int64_t Mt, int nranks
         total += (b + g - 1) / g * g;
     };
     const vk::AxPlan axp = vk::ax_plan(N, Mx);
-    add(Mx * ld, 8);                                   // X
+    add(Mx * ld, 8);                                   // X (as doubles; fp32 storage: below)
     add(Mx, 8), add(Mx, 8), add(ld, 8);                // mave, msig, y
     add((int64_t)axp.nslots * vk::kMaxRhs * ld, 8);    // ax_part
     add((int64_t)red_capacity(Mx), 8), add((int64_t)red_capacity(Mx), 8);
@@ -2061,8 +2190,17 @@ extern "C" vampomi_status vampomi_dev_mem_plan(int64_t N, int64_t Mt, int nranks
         for (int q = 0; q < 3; ++q) add(Mx, 8);
     }
     (void)writer;  // the writer's staging is pinned host memory (writer.h), allocated with every context
+    // fp32 storage holds the same Mx x ld elements in half the bytes: the plan
+    // is the fp64 plan less exactly that saving (the allocator's rounding of
+    // the smaller block is not modelled: at most one granule either way)
+    if (storage == VAMPOMI_STORE_F32) total -= Mx * ld * 4;
     *bytes = total;
     return VAMPOMI_OK;
+}
+
+extern "C" vampomi_status vampomi_dev_mem_plan(int64_t N, int64_t Mt, int nranks, int rank, int cus, int probit,
+                                               int writer, int64_t* bytes) {
+    return vampomi_dev_mem_plan_storage(N, Mt, nranks, rank, cus, probit, writer, VAMPOMI_STORE_F64, bytes);
 }
 
 // the operator's kernel as rocprofv3 prints it, for the context's plan
@@ -2074,9 +2212,9 @@ static std::string op_name(const vampomi_ctx* c, int K) {
     if (K == 1 + vk::kOpPlain) {  // the head-start launch
         vk::OpPlan h{};
         if (!vk::team_plain_plan(c->N, std::max<int64_t>(c->M, 1), cus, p, &h)) return "(no head-start plan)";
-        return vk::team_kernel_name(K, h);
+        return vk::team_kernel_name(K, h, c->f32());
     }
-    return vk::op_kernel_name(K, p);
+    return vk::op_kernel_name(K, p, c->f32());
 }
 
 extern "C" vampomi_status vampomi_dev_read_ceiling(vampomi_ctx* c, int reps, double* us_med, double* bytes,
@@ -2094,13 +2232,13 @@ extern "C" vampomi_status vampomi_dev_read_ceiling(vampomi_ctx* c, int reps, dou
     int best_kind = -1;
     for (int kind = 0; kind < 2; ++kind) {
         double nb = 0.0;
-        if (vk::stream_read(c->X, n, kind, c->cus, c->st, vk::Timing{}, c->red_part, &nb) != hipSuccess) {
+        if (vk::stream_read(c->X, c->f32(), n, kind, c->cus, c->st, vk::Timing{}, c->red_part, &nb) != hipSuccess) {
             (void)hipGetLastError();
             continue;  // the buffer is too small for this shape
         }
         std::vector<float> ms((size_t)reps);
         for (int r = 0; r < reps; ++r) {
-            HIPCHK(vk::stream_read(c->X, n, kind, c->cus, c->st, vk::Timing{a, b}, c->red_part, &nb));
+            HIPCHK(vk::stream_read(c->X, c->f32(), n, kind, c->cus, c->st, vk::Timing{a, b}, c->red_part, &nb));
             HIPCHK(hipEventSynchronize(b));
             HIPCHK(hipEventElapsedTime(&ms[(size_t)r], a, b));
         }
@@ -2125,10 +2263,11 @@ extern "C" vampomi_status vampomi_dev_kernel_name(const vampomi_ctx* c, int whic
                                                   int cap) {
     if (!c || !out || cap < 1) return fail(VAMPOMI_ERR_ARG, "bad argument");
     // which = 3: mode carries N (the operator's instantiation depends on it)
-    const std::string n = which == 2   ? vk::loo_kernel_name(c->loo_variant)
+    const int f32 = c->f32();
+    const std::string n = which == 2   ? vk::loo_kernel_name(c->loo_variant, f32)
                           : which == 3 ? op_name(c, K)
-                          : which == 0 ? vk::ax_kernel_name(K, mode == 1, c->axp)
-                                       : vk::kernel_name(1, K, mode, c->atx_variant);
+                          : which == 0 ? vk::ax_kernel_name(K, mode == 1, c->axp, f32)
+                                       : vk::kernel_name(1, K, mode, c->atx_variant, f32);
     std::snprintf(out, (size_t)cap, "%s", n.c_str());
     return VAMPOMI_OK;
 }

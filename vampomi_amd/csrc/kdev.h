@@ -10,6 +10,34 @@
 namespace vk {
 
 typedef double v2d __attribute__((ext_vector_type(2)));
+typedef float v2f __attribute__((ext_vector_type(2)));
+
+// A row pair of a column of X: one 16-byte load of a double column, or one
+// 8-byte load of a float column.  The lane owns the same two rows either way,
+// so every sum over a column runs in the same order for both storages.  The
+// pair stays as loaded (xpair_t) until it is used and is widened there
+// (widen: exact; nothing for doubles), so a load issued ahead is not waited
+// for by a conversion.  NT: nontemporal (the streaming passes)
+template <class E>
+struct XPair;
+template <>
+struct XPair<double> {
+    typedef v2d type;
+};
+template <>
+struct XPair<float> {
+    typedef v2f type;
+};
+template <class E>
+using xpair_t = typename XPair<E>::type;
+
+template <bool NT, class E>
+__device__ __forceinline__ xpair_t<E> ldx(const E* p) {
+    if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const xpair_t<E>*>(p));
+    return *reinterpret_cast<const xpair_t<E>*>(p);
+}
+__device__ __forceinline__ v2d widen(v2d x) { return x; }
+__device__ __forceinline__ v2d widen(v2f x) { return v2d{(double)x.x, (double)x.y}; }
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

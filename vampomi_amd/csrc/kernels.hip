@@ -165,10 +165,6 @@ __device__ bool red_finish(const RedOut& ro, int nq, double* /*lds4*/, double* k
     return true;
 }
 
-__device__ __forceinline__ v2d ld_stream(const double* p) {
-    return __builtin_nontemporal_load(reinterpret_cast<const v2d*>(p));
-}
-
 __device__ __forceinline__ v2d ld2(const double* p) { return *reinterpret_cast<const v2d*>(p); }
 
 // x^1.5, correctly rounded except in hard midpoint cases (glibc's pow is within
@@ -261,8 +257,8 @@ static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // (the CG direction update, src/vamp.cpp:738-739, as every consumer of the new
 // direction forms it).  The kernel stores nothing but its partials, so the
 // compiler keeps the per-marker loads scalar.
-template <int K, int R, int U, bool NT, bool FU>
-__device__ __forceinline__ void ax_piece(const double* __restrict__ X, int64_t ld, int64_t N,
+template <int K, int R, int U, bool NT, bool FU, class XE>
+__device__ __forceinline__ void ax_piece(const XE* __restrict__ X, int64_t ld, int64_t N,
                                          const double* __restrict__ mave, const double* __restrict__ msig,
                                          const CPtrs& xs, const AxFuse& fu, const double (&bk)[K], int64_t j0,
                                          int64_t i0, int64_t i1, double (&acc)[K][R]) {
@@ -270,15 +266,15 @@ __device__ __forceinline__ void ax_piece(const double* __restrict__ X, int64_t l
     int64_t off[P];  // invalid pieces read row 0 of the column (in bounds) and are discarded at the store
 #pragma unroll
     for (int q = 0; q < P; ++q) off[q] = (j0 + 128 * q < N) ? 128 * q : -j0;
-    const double* col = X + i0 * ld + j0;
+    const XE* col = X + i0 * ld + j0;
     int64_t i = i0;
     for (; i + (U - 1) < i1; i += U) {
-        v2d xv[U][P];
+        xpair_t<XE> xv[U][P];
 #pragma unroll
         for (int u = 0; u < U; ++u)
 #pragma unroll
             for (int q = 0; q < P; ++q)
-                xv[u][q] = NT ? ld_stream(col + (int64_t)u * ld + off[q]) : ld2(col + (int64_t)u * ld + off[q]);
+                xv[u][q] = ldx<NT>(col + (int64_t)u * ld + off[q]);
         double xk[U][K];
 #pragma unroll
         for (int u = 0; u < U; ++u)
@@ -294,17 +290,17 @@ __device__ __forceinline__ void ax_piece(const double* __restrict__ X, int64_t l
                 const double w = sg * xk[u][k];
 #pragma unroll
                 for (int q = 0; q < P; ++q) {
-                    acc[k][2 * q] += (xv[u][q].x - ave) * w;
-                    acc[k][2 * q + 1] += (xv[u][q].y - ave) * w;
+                    acc[k][2 * q] += (widen(xv[u][q]).x - ave) * w;
+                    acc[k][2 * q + 1] += (widen(xv[u][q]).y - ave) * w;
                 }
             }
         }
         col += (int64_t)U * ld;
     }
     for (; i < i1; ++i) {
-        v2d xv[P];
+        xpair_t<XE> xv[P];
 #pragma unroll
-        for (int q = 0; q < P; ++q) xv[q] = NT ? ld_stream(col + off[q]) : ld2(col + off[q]);
+        for (int q = 0; q < P; ++q) xv[q] = ldx<NT>(col + off[q]);
         double xk[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) xk[k] = FU ? fu.z.p[k][i] + bk[k] * xs.p[k][i] : xs.p[k][i];
@@ -315,8 +311,8 @@ __device__ __forceinline__ void ax_piece(const double* __restrict__ X, int64_t l
             const double w = sg * xk[k];
 #pragma unroll
             for (int q = 0; q < P; ++q) {
-                acc[k][2 * q] += (xv[q].x - ave) * w;
-                acc[k][2 * q + 1] += (xv[q].y - ave) * w;
+                acc[k][2 * q] += (widen(xv[q]).x - ave) * w;
+                acc[k][2 * q + 1] += (widen(xv[q]).y - ave) * w;
             }
         }
         col += ld;
@@ -346,13 +342,13 @@ __device__ __forceinline__ void ax_zero(double (&acc)[K][R]) {
         for (int r = 0; r < R; ++r) acc[k][r] = 0.0;
 }
 
-template <int K, int R, int U, bool NT, bool FU>
-__global__ __launch_bounds__(kBlock) void ax_partial_kernel(const double* __restrict__ X, int64_t ld,
-                                                            int64_t N, int64_t M,
-                                                            const double* __restrict__ mave,
-                                                            const double* __restrict__ msig, CPtrs xs,
-                                                            int64_t tiles, int64_t span, int64_t nband,
-                                                            double* __restrict__ part, AxFuse fu) {
+// (the body of ax_partial_kernel and ax_partial_kernel_f32: XE is X's element type)
+template <int K, int R, int U, bool NT, bool FU, class XE>
+__device__ __forceinline__ void ax_partial_body(const XE* __restrict__ X, int64_t ld, int64_t N, int64_t M,
+                                                const double* __restrict__ mave,
+                                                const double* __restrict__ msig, const CPtrs& xs, int64_t tiles,
+                                                int64_t span, int64_t nband, double* __restrict__ part,
+                                                const AxFuse& fu) {
     if (fu.gate && !*fu.gate) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t g = blockIdx.x, G = gridDim.x;
@@ -408,6 +404,26 @@ __global__ __launch_bounds__(kBlock) void ax_partial_kernel(const double* __rest
         ax_piece<K, R, U, NT, FU>(X, ld, N, mave, msig, xs, fu, bk, j0, i0, i1, acc);
         ax_store<K, R>(part, g - (t * M) / span, ld, N, j0, acc);
     }
+}
+
+template <int K, int R, int U, bool NT, bool FU>
+__global__ __launch_bounds__(kBlock) void ax_partial_kernel(const double* __restrict__ X, int64_t ld,
+                                                            int64_t N, int64_t M,
+                                                            const double* __restrict__ mave,
+                                                            const double* __restrict__ msig, CPtrs xs,
+                                                            int64_t tiles, int64_t span, int64_t nband,
+                                                            double* __restrict__ part, AxFuse fu) {
+    ax_partial_body<K, R, U, NT, FU>(X, ld, N, M, mave, msig, xs, tiles, span, nband, part, fu);
+}
+
+template <int K, int R, int U, bool NT, bool FU>
+__global__ __launch_bounds__(kBlock) void ax_partial_kernel_f32(const float* __restrict__ X, int64_t ld,
+                                                                int64_t N, int64_t M,
+                                                                const double* __restrict__ mave,
+                                                                const double* __restrict__ msig, CPtrs xs,
+                                                                int64_t tiles, int64_t span, int64_t nband,
+                                                                double* __restrict__ part, AxFuse fu) {
+    ax_partial_body<K, R, U, NT, FU>(X, ld, N, M, mave, msig, xs, tiles, span, nband, part, fu);
 }
 
 // tuning table (rows per lane R, markers in flight U, nontemporal loads)
@@ -472,13 +488,24 @@ AxPlan ax_plan_for(int64_t N, int64_t M, int cus, int variant) {
 template <int K, int R, int U, bool NT>
 static void launch_ax(const Shard& s, const AxPlan& pl, CPtrs x, double* part, hipStream_t st, const Timing& tm,
                       const AxFuse& fu) {
+    if (s.f32) {
+        if (fu.z.p[0])
+            hipExtLaunchKernelGGL((ax_partial_kernel_f32<K, R, U, NT, true>), dim3(pl.groups), dim3(kBlock), 0, st,
+                                  tm.start, tm.stop, 0, s.x32(), s.ld, s.N, s.M, s.mave, s.msig, x, pl.tiles,
+                                  pl.span, pl.nband, part, fu);
+        else
+            hipExtLaunchKernelGGL((ax_partial_kernel_f32<K, R, U, NT, false>), dim3(pl.groups), dim3(kBlock), 0, st,
+                                  tm.start, tm.stop, 0, s.x32(), s.ld, s.N, s.M, s.mave, s.msig, x, pl.tiles,
+                                  pl.span, pl.nband, part, fu);
+        return;
+    }
     if (fu.z.p[0])
         hipExtLaunchKernelGGL((ax_partial_kernel<K, R, U, NT, true>), dim3(pl.groups), dim3(kBlock), 0, st, tm.start,
-                              tm.stop, 0, s.X, s.ld, s.N, s.M, s.mave, s.msig, x, pl.tiles, pl.span, pl.nband, part,
-                              fu);
+                              tm.stop, 0, s.x64(), s.ld, s.N, s.M, s.mave, s.msig, x, pl.tiles, pl.span, pl.nband,
+                              part, fu);
     else
         hipExtLaunchKernelGGL((ax_partial_kernel<K, R, U, NT, false>), dim3(pl.groups), dim3(kBlock), 0, st,
-                              tm.start, tm.stop, 0, s.X, s.ld, s.N, s.M, s.mave, s.msig, x, pl.tiles, pl.span,
+                              tm.start, tm.stop, 0, s.x64(), s.ld, s.N, s.M, s.mave, s.msig, x, pl.tiles, pl.span,
                               pl.nband, part, fu);
 }
 
@@ -574,68 +601,99 @@ hipError_t ax_reduce(const AxPlan& pl, int K, int64_t N, int64_t ld, const doubl
 // shapes as tools/hbm_ceiling's lock and chunk variants).  The sums feed a
 // store that never happens (the comparison with the NaN `never`), so no load
 // is dead.
-__global__ __launch_bounds__(512) void stream_lock_kernel(const double* __restrict__ x, int64_t units,
-                                                          double never, double* __restrict__ sink) {
+template <class XE>
+__device__ __forceinline__ void stream_lock_body(const XE* __restrict__ x, int64_t units, double never,
+                                                 double* __restrict__ sink) {
     constexpr int U = 8;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t b = units * blockIdx.x / gridDim.x * 1024, e = units * (blockIdx.x + 1) / gridDim.x * 1024;
     double a0 = 0.0, a1 = 0.0;
     int64_t j = b + 128 * wave + 2 * lane;
     for (; j + 1024 * (U - 1) < e; j += 1024 * U) {
-        v2d v[U];
+        xpair_t<XE> v[U];
 #pragma unroll
-        for (int t = 0; t < U; ++t) v[t] = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(x + j + 1024 * t));
+        for (int t = 0; t < U; ++t) v[t] = ldx<true>(x + j + 1024 * t);
 #pragma unroll
         for (int t = 0; t < U; ++t) {
-            a0 += v[t].x;
-            a1 += v[t].y;
+            a0 += widen(v[t]).x;
+            a1 += widen(v[t]).y;
         }
         __syncthreads();
     }
     for (; j < e; j += 1024) {
-        const v2d v = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(x + j));
+        const v2d v = widen(ldx<true>(x + j));
         a0 += v.x;
         a1 += v.y;
     }
     if (a0 + a1 == never) sink[0] = a0;
 }
 
-__global__ __launch_bounds__(256) void stream_chunk_kernel(const double* __restrict__ x, int64_t nchunks,
-                                                           double never, double* __restrict__ sink) {
+__global__ __launch_bounds__(512) void stream_lock_kernel(const double* __restrict__ x, int64_t units,
+                                                          double never, double* __restrict__ sink) {
+    stream_lock_body(x, units, never, sink);
+}
+
+__global__ __launch_bounds__(512) void stream_lock_kernel_f32(const float* __restrict__ x, int64_t units,
+                                                              double never, double* __restrict__ sink) {
+    stream_lock_body(x, units, never, sink);
+}
+
+template <class XE>
+__device__ __forceinline__ void stream_chunk_body(const XE* __restrict__ x, int64_t nchunks, double never,
+                                                  double* __restrict__ sink) {
     constexpr int U = 8;
-    constexpr int64_t CW = 1 << 17;  // 1 MiB of doubles per wave
+    constexpr int64_t CW = 1 << 17;  // elements per wave (1 MiB of doubles, 512 KiB of floats)
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= nchunks) return;
     double a0 = 0.0, a1 = 0.0;
     for (int64_t j = w * CW + 2 * lane; j < (w + 1) * CW; j += 128 * U) {
-        v2d v[U];
+        xpair_t<XE> v[U];
 #pragma unroll
-        for (int t = 0; t < U; ++t) v[t] = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(x + j + 128 * t));
+        for (int t = 0; t < U; ++t) v[t] = ldx<true>(x + j + 128 * t);
 #pragma unroll
         for (int t = 0; t < U; ++t) {
-            a0 += v[t].x;
-            a1 += v[t].y;
+            a0 += widen(v[t]).x;
+            a1 += widen(v[t]).y;
         }
     }
     if (a0 + a1 == never) sink[0] = a0;
 }
 
-hipError_t stream_read(const double* x, int64_t n, int kind, int cus, hipStream_t st, const Timing& tm,
+__global__ __launch_bounds__(256) void stream_chunk_kernel(const double* __restrict__ x, int64_t nchunks,
+                                                           double never, double* __restrict__ sink) {
+    stream_chunk_body(x, nchunks, never, sink);
+}
+
+__global__ __launch_bounds__(256) void stream_chunk_kernel_f32(const float* __restrict__ x, int64_t nchunks,
+                                                               double never, double* __restrict__ sink) {
+    stream_chunk_body(x, nchunks, never, sink);
+}
+
+hipError_t stream_read(const void* x, int f32, int64_t n, int kind, int cus, hipStream_t st, const Timing& tm,
                        double* sink, double* bytes) {
     const double never = __builtin_nan("");
+    const double esize = f32 ? 4.0 : 8.0;
     if (kind == 0) {
         const int64_t units = n / 1024;
         if (units < cus) return hipErrorInvalidValue;
-        *bytes = 8.0 * (double)(units * 1024);
-        hipExtLaunchKernelGGL(stream_lock_kernel, dim3(cus), dim3(512), 0, st, tm.start, tm.stop, 0, x, units, never,
-                              sink);
+        *bytes = esize * (double)(units * 1024);
+        if (f32)
+            hipExtLaunchKernelGGL(stream_lock_kernel_f32, dim3(cus), dim3(512), 0, st, tm.start, tm.stop, 0,
+                                  static_cast<const float*>(x), units, never, sink);
+        else
+            hipExtLaunchKernelGGL(stream_lock_kernel, dim3(cus), dim3(512), 0, st, tm.start, tm.stop, 0,
+                                  static_cast<const double*>(x), units, never, sink);
     } else {
         const int64_t nch = n / (1 << 17);
         if (nch < 1) return hipErrorInvalidValue;
-        *bytes = 8.0 * (double)(nch << 17);
-        hipExtLaunchKernelGGL(stream_chunk_kernel, dim3((unsigned)((nch + 3) / 4)), dim3(256), 0, st, tm.start,
-                              tm.stop, 0, x, nch, never, sink);
+        *bytes = esize * (double)(nch << 17);
+        if (f32)
+            hipExtLaunchKernelGGL(stream_chunk_kernel_f32, dim3((unsigned)((nch + 3) / 4)), dim3(256), 0, st,
+                                  tm.start, tm.stop, 0, static_cast<const float*>(x), nch, never, sink);
+        else
+            hipExtLaunchKernelGGL(stream_chunk_kernel, dim3((unsigned)((nch + 3) / 4)), dim3(256), 0, st, tm.start,
+                                  tm.stop, 0, static_cast<const double*>(x), nch, never, sink);
     }
     return hipGetLastError();
 }
@@ -663,19 +721,19 @@ hipError_t vec_div(int K, int64_t n, int64_t /*ld*/, Ptrs v, double div, hipStre
 // per loop trip.  Every u value loaded serves G markers.  The wave's partial
 // dots are reduced with an xor butterfly; mode 1 fuses the lmmse_mult
 // epilogue (src/vamp.cpp:656-659).
-template <int G, int K, int MODE, int UJ, bool NT>
-__global__ __launch_bounds__(kBlock) void atx_kernel(const double* __restrict__ X, int64_t ld, int64_t N, int64_t M,
-                                                     const double* __restrict__ mave,
-                                                     const double* __restrict__ msig, CPtrs u, Ptrs out,
-                                                     double scale, double tau, double gam2, CPtrs pv,
-                                                     const int* __restrict__ gate, CPtrs zf,
-                                                     const double* __restrict__ beta, Ptrs sraw) {
+// (the body of atx_kernel and atx_kernel_f32: XE is X's element type)
+template <int G, int K, int MODE, int UJ, bool NT, class XE>
+__device__ __forceinline__ void atx_body(const XE* __restrict__ X, int64_t ld, int64_t N, int64_t M,
+                                         const double* __restrict__ mave, const double* __restrict__ msig,
+                                         const CPtrs& u, const Ptrs& out, double scale, double tau, double gam2,
+                                         const CPtrs& pv, const int* __restrict__ gate, const CPtrs& zf,
+                                         const double* __restrict__ beta, const Ptrs& sraw) {
     if (gate && !*gate) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t m0 = ((int64_t)blockIdx.x * (blockDim.x >> 6) + wave) * G;
     double acc[G][K];
     double mu[G];
-    const double* col[G];
+    const XE* col[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         const int64_t m = (m0 + g < M) ? m0 + g : M - 1;  // clamp: in-bounds, discarded
@@ -686,11 +744,12 @@ __global__ __launch_bounds__(kBlock) void atx_kernel(const double* __restrict__ 
     }
     int64_t j = 2 * lane;
     for (; j + 128 * (UJ - 1) < N; j += 128 * UJ) {
-        v2d uu[UJ][K], xx[UJ][G];
+        v2d uu[UJ][K];
+        xpair_t<XE> xx[UJ][G];
 #pragma unroll
         for (int t = 0; t < UJ; ++t)
 #pragma unroll
-            for (int g = 0; g < G; ++g) xx[t][g] = NT ? ld_stream(col[g] + j + 128 * t) : ld2(col[g] + j + 128 * t);
+            for (int g = 0; g < G; ++g) xx[t][g] = ldx<NT>(col[g] + j + 128 * t);
 #pragma unroll
         for (int t = 0; t < UJ; ++t)
 #pragma unroll
@@ -699,7 +758,7 @@ __global__ __launch_bounds__(kBlock) void atx_kernel(const double* __restrict__ 
         for (int g = 0; g < G; ++g) {
 #pragma unroll
             for (int t = 0; t < UJ; ++t) {
-                const double d0 = xx[t][g].x - mu[g], d1 = xx[t][g].y - mu[g];
+                const double d0 = widen(xx[t][g]).x - mu[g], d1 = widen(xx[t][g]).y - mu[g];
 #pragma unroll
                 for (int k = 0; k < K; ++k) {
                     acc[g][k] += d0 * uu[t][k].x;
@@ -709,14 +768,15 @@ __global__ __launch_bounds__(kBlock) void atx_kernel(const double* __restrict__ 
         }
     }
     for (; j < N; j += 128) {  // tail; j+1 may be the zero pad row (u pad is zero too)
-        v2d uu[K], xx[G];
+        v2d uu[K];
+        xpair_t<XE> xx[G];
 #pragma unroll
-        for (int g = 0; g < G; ++g) xx[g] = NT ? ld_stream(col[g] + j) : ld2(col[g] + j);
+        for (int g = 0; g < G; ++g) xx[g] = ldx<NT>(col[g] + j);
 #pragma unroll
         for (int k = 0; k < K; ++k) uu[k] = ld2(u.p[k] + j);
 #pragma unroll
         for (int g = 0; g < G; ++g) {
-            const double d0 = xx[g].x - mu[g], d1 = xx[g].y - mu[g];
+            const double d0 = widen(xx[g]).x - mu[g], d1 = widen(xx[g]).y - mu[g];
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 acc[g][k] += d0 * uu[k].x;
@@ -745,6 +805,26 @@ __global__ __launch_bounds__(kBlock) void atx_kernel(const double* __restrict__ 
     }
 }
 
+template <int G, int K, int MODE, int UJ, bool NT>
+__global__ __launch_bounds__(kBlock) void atx_kernel(const double* __restrict__ X, int64_t ld, int64_t N, int64_t M,
+                                                     const double* __restrict__ mave,
+                                                     const double* __restrict__ msig, CPtrs u, Ptrs out,
+                                                     double scale, double tau, double gam2, CPtrs pv,
+                                                     const int* __restrict__ gate, CPtrs zf,
+                                                     const double* __restrict__ beta, Ptrs sraw) {
+    atx_body<G, K, MODE, UJ, NT>(X, ld, N, M, mave, msig, u, out, scale, tau, gam2, pv, gate, zf, beta, sraw);
+}
+
+template <int G, int K, int MODE, int UJ, bool NT>
+__global__ __launch_bounds__(kBlock) void atx_kernel_f32(const float* __restrict__ X, int64_t ld, int64_t N,
+                                                         int64_t M, const double* __restrict__ mave,
+                                                         const double* __restrict__ msig, CPtrs u, Ptrs out,
+                                                         double scale, double tau, double gam2, CPtrs pv,
+                                                         const int* __restrict__ gate, CPtrs zf,
+                                                         const double* __restrict__ beta, Ptrs sraw) {
+    atx_body<G, K, MODE, UJ, NT>(X, ld, N, M, mave, msig, u, out, scale, tau, gam2, pv, gate, zf, beta, sraw);
+}
+
 // tuning table (markers per wave G, 128-row steps per trip UJ, nontemporal)
 struct AtxVariant { int G, UJ; bool NT; };
 static constexpr AtxVariant kAtxVariants[] = {
@@ -759,15 +839,17 @@ int atx_variant_count() { return kNumAtxVariants; }
 bool atx_variant_ok(int v) { return v >= -1 && v < kNumAtxVariants; }
 
 // rocprofv3 kernel name of the launch that ax_partial / atx would make now
-std::string kernel_name(int which, int K, int mode, int variant) {
+std::string kernel_name(int which, int K, int mode, int variant, int f32) {
     char b[160];
+    const char* sfx = f32 ? "_f32" : "";
     if (which == 0) {
         const AxVariant& v = kAxVariants[variant >= 0 && variant < kNumAxVariants ? variant : 0];
-        std::snprintf(b, sizeof b, "ax_partial_kernel<%d, %d, %d, %s, %s>", K, v.R, v.U, v.NT ? "true" : "false",
-                      mode == 1 ? "true" : "false");
+        std::snprintf(b, sizeof b, "ax_partial_kernel%s<%d, %d, %d, %s, %s>", sfx, K, v.R, v.U,
+                      v.NT ? "true" : "false", mode == 1 ? "true" : "false");
     } else {
         const AtxVariant& v = kAtxVariants[atx_variant_for(variant, K)];
-        std::snprintf(b, sizeof b, "atx_kernel<%d, %d, %d, %d, %s>", v.G, K, mode, v.UJ, v.NT ? "true" : "false");
+        std::snprintf(b, sizeof b, "atx_kernel%s<%d, %d, %d, %d, %s>", sfx, v.G, K, mode, v.UJ,
+                      v.NT ? "true" : "false");
     }
     return b;
 }
@@ -780,9 +862,14 @@ static void launch_atx(const Shard& s, CPtrs u, Ptrs out, double scale, double t
     // two waves per workgroup: a finer dispatch grain than four (C2: -2..4%,
     // profiles/r01_kbench_ax_swap.txt); VAMPOMI_ATX_WPB: tuning experiments
     static const int wpb = std::getenv("VAMPOMI_ATX_WPB") ? std::max(1, std::min(4, std::atoi(std::getenv("VAMPOMI_ATX_WPB")))) : 2;
-    hipExtLaunchKernelGGL((atx_kernel<G, K, MODE, UJ, NT>), dim3((unsigned)cdiv(s.M, wpb * G)), dim3(64 * wpb), 0, st,
-                          tm.start, tm.stop, 0, s.X, s.ld, s.N, s.M, s.mave, s.msig, u, out, scale, tau, gam2, p,
-                          gate, zf, beta, sraw);
+    if (s.f32)
+        hipExtLaunchKernelGGL((atx_kernel_f32<G, K, MODE, UJ, NT>), dim3((unsigned)cdiv(s.M, wpb * G)),
+                              dim3(64 * wpb), 0, st, tm.start, tm.stop, 0, s.x32(), s.ld, s.N, s.M, s.mave, s.msig, u,
+                              out, scale, tau, gam2, p, gate, zf, beta, sraw);
+    else
+        hipExtLaunchKernelGGL((atx_kernel<G, K, MODE, UJ, NT>), dim3((unsigned)cdiv(s.M, wpb * G)), dim3(64 * wpb), 0,
+                              st, tm.start, tm.stop, 0, s.x64(), s.ld, s.N, s.M, s.mave, s.msig, u, out, scale, tau,
+                              gam2, p, gate, zf, beta, sraw);
 }
 
 template <int K, int MODE>
@@ -920,17 +1007,17 @@ bool op_supported(int64_t N, int K) {
 }
 
 // one column in registers: its X rows and the marker's mean
-template <int K, int S>
+template <int K, int S, class XE = double>
 struct OpCol {
-    v2d x[S];
+    xpair_t<XE> x[S];  // as loaded (widened where it is used)
     double mu;
 };
 
-template <int K, int S>
-__global__ __launch_bounds__(kOpThreads) void atax_kernel(const double* __restrict__ X, int64_t ld, int64_t N,
-                                                          int64_t M, const double* __restrict__ mave,
-                                                          const double* __restrict__ msig, OpArgs a,
-                                                          const int* __restrict__ gate) {
+// (the body of atax_kernel and atax_kernel_f32: XE is X's element type)
+template <int K, int S, class XE>
+__device__ __forceinline__ void atax_body(const XE* __restrict__ X, int64_t ld, int64_t N, int64_t M,
+                                          const double* __restrict__ mave, const double* __restrict__ msig,
+                                          const OpArgs& a, const int* __restrict__ gate) {
     if (gate && !*gate) return;
     // LDS: q (K x NL; each thread only ever touches its own rows), a zero
     // pair, then 2 x kOpWaves x K dot partials
@@ -978,23 +1065,24 @@ __global__ __launch_bounds__(kOpThreads) void atax_kernel(const double* __restri
     for (int k = 0; k < K; ++k) dpacc[k] = 0.0;
     // columns in registers: three where they fit beside acc, else two
     constexpr int NB = K * S <= 16 ? 3 : 2;
-    OpCol<K, S> cb[NB];
-    auto load = [&](OpCol<K, S>& c, int64_t m) {
+    OpCol<K, S, XE> cb[NB];
+    auto load = [&](OpCol<K, S, XE>& c, int64_t m) {
         const char* col = reinterpret_cast<const char*>(X + m * ld);
 #pragma unroll
         for (int s = 0; s < S; ++s)
-            if (OP_OK(s)) c.x[s] = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(col + (unsigned)(OP_J(s) * 8)));
+            if (OP_OK(s))
+                c.x[s] = ldx<true>(reinterpret_cast<const XE*>(col + (unsigned)(OP_J(s) * (int)sizeof(XE))));
         c.mu = mave[m];
     };
     // dot partials of column c -> s_part[par][wave][k]
-    auto dots = [&](const OpCol<K, S>& c, int par) {
+    auto dots = [&](const OpCol<K, S, XE>& c, int par) {
         double v[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) v[k] = 0.0;
 #pragma unroll
         for (int s = 0; s < S; ++s) {
             if (!OP_OK(s)) continue;
-            const double dx = c.x[s].x - c.mu, dy = c.x[s].y - c.mu;
+            const double dx = widen(c.x[s]).x - c.mu, dy = widen(c.x[s]).y - c.mu;
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 const v2d q = *reinterpret_cast<const v2d*>(q_lds + k * NL + OP_J(s));  // q[N] = 0 for odd N
@@ -1016,7 +1104,7 @@ __global__ __launch_bounds__(kOpThreads) void atax_kernel(const double* __restri
         }
     };
     // the column's d (all waves, identically) and acc += (x - mave)*msig*d
-    auto finish = [&](const OpCol<K, S>& c, int64_t m, int par) {
+    auto finish = [&](const OpCol<K, S, XE>& c, int64_t m, int par) {
         const double sg = msig[m];
         double cc[K];
 #pragma unroll
@@ -1040,7 +1128,7 @@ __global__ __launch_bounds__(kOpThreads) void atax_kernel(const double* __restri
 #pragma unroll
         for (int s = 0; s < S; ++s) {
             if (!OP_OK(s)) continue;
-            const double dx = c.x[s].x - c.mu, dy = c.x[s].y - c.mu;
+            const double dx = widen(c.x[s]).x - c.mu, dy = widen(c.x[s]).y - c.mu;
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 acc[k][s].x += dx * cc[k];
@@ -1050,7 +1138,7 @@ __global__ __launch_bounds__(kOpThreads) void atax_kernel(const double* __restri
     };
     // NB columns in registers: m is finished while m+1 .. m+NB-1 load; the
     // buffer m frees takes m+NB.  Dot partials alternate between two LDS slots.
-    auto step = [&](OpCol<K, S>& cur, OpCol<K, S>& nxt, int64_t m, int par) {
+    auto step = [&](OpCol<K, S, XE>& cur, OpCol<K, S, XE>& nxt, int64_t m, int par) {
         finish(cur, m, par);
         if (m + NB < me) load(cur, m + NB);
         if (m + 1 < me) {
@@ -1108,10 +1196,26 @@ __global__ __launch_bounds__(kOpThreads) void atax_kernel(const double* __restri
     if (wave == 0) ticket_sum_blocks<K>(ro);
 }
 
-std::string op_kernel_name(int K, const OpPlan& pl) {
-    if (pl.T > 0) return team_kernel_name(K, pl);
+template <int K, int S>
+__global__ __launch_bounds__(kOpThreads) void atax_kernel(const double* __restrict__ X, int64_t ld, int64_t N,
+                                                          int64_t M, const double* __restrict__ mave,
+                                                          const double* __restrict__ msig, OpArgs a,
+                                                          const int* __restrict__ gate) {
+    atax_body<K, S>(X, ld, N, M, mave, msig, a, gate);
+}
+
+template <int K, int S>
+__global__ __launch_bounds__(kOpThreads) void atax_kernel_f32(const float* __restrict__ X, int64_t ld, int64_t N,
+                                                              int64_t M, const double* __restrict__ mave,
+                                                              const double* __restrict__ msig, OpArgs a,
+                                                              const int* __restrict__ gate) {
+    atax_body<K, S>(X, ld, N, M, mave, msig, a, gate);
+}
+
+std::string op_kernel_name(int K, const OpPlan& pl, int f32) {
+    if (pl.T > 0) return team_kernel_name(K, pl, f32);
     char b[96];
-    std::snprintf(b, sizeof b, "atax_kernel<%d, %d>", K, pl.S);
+    std::snprintf(b, sizeof b, "atax_kernel%s<%d, %d>", f32 ? "_f32" : "", K, pl.S);
     return b;
 }
 
@@ -1139,10 +1243,19 @@ static hipError_t launch_op(const Shard& s, const OpPlan& pl, const OpArgs& a, h
                             const int* gate) {
     const size_t lds = ((size_t)K * (s.N + 1 + (s.N & 1)) + 2 + 2 * kOpWaves * K) * sizeof(double);
     static std::atomic<unsigned long long> allowed{0};  // more than 64 KiB of dynamic LDS must be allowed explicitly
+    if (s.f32) {
+        static std::atomic<unsigned long long> allowed32{0};
+        if (const hipError_t e =
+                lds_allow(reinterpret_cast<const void*>(&atax_kernel_f32<K, S>), allowed32, 160 * 1024))
+            return e;
+        hipExtLaunchKernelGGL((atax_kernel_f32<K, S>), dim3(pl.grid), dim3(kOpThreads), lds, st, tm.start, tm.stop, 0,
+                              s.x32(), s.ld, s.N, s.M, s.mave, s.msig, a, gate);
+        return hipSuccess;
+    }
     if (const hipError_t e = lds_allow(reinterpret_cast<const void*>(&atax_kernel<K, S>), allowed, 160 * 1024))
         return e;
-    hipExtLaunchKernelGGL((atax_kernel<K, S>), dim3(pl.grid), dim3(kOpThreads), lds, st, tm.start, tm.stop, 0, s.X,
-                          s.ld, s.N, s.M, s.mave, s.msig, a, gate);
+    hipExtLaunchKernelGGL((atax_kernel<K, S>), dim3(pl.grid), dim3(kOpThreads), lds, st, tm.start, tm.stop, 0,
+                          s.x64(), s.ld, s.N, s.M, s.mave, s.msig, a, gate);
     return hipSuccess;
 }
 
@@ -1254,16 +1367,19 @@ hipError_t op_reduce(const OpPlan& pl, int K, int64_t N, int64_t ld, const doubl
 // ---------------------------------------------------------------------------
 // marker statistics (src/data.cpp:233-283): one wave per marker, two passes
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void stats_kernel(const double* __restrict__ X, int64_t ld, int64_t N, int64_t M,
-                                                       double nonas, double alpha_scale, double* __restrict__ mave,
-                                                       double* __restrict__ msig) {
+// (the body of stats_kernel and stats_kernel_f32: the statistics of the stored
+// values, widened, summed in fp64)
+template <class XE>
+__device__ __forceinline__ void stats_body(const XE* __restrict__ X, int64_t ld, int64_t N, int64_t M, double nonas,
+                                           double alpha_scale, double* __restrict__ mave,
+                                           double* __restrict__ msig) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t m = (int64_t)blockIdx.x * 4 + wave;
     if (m >= M) return;
-    const double* col = X + m * ld;
+    const XE* col = X + m * ld;
     double s = 0.0;
     for (int64_t j = 2 * lane; j < N; j += 128) {
-        const v2d x = ld2(col + j);
+        const v2d x = widen(ldx<false>(col + j));
         s += x.x;
         if (j + 1 < N) s += x.y;
     }
@@ -1271,7 +1387,7 @@ __global__ __launch_bounds__(kBlock) void stats_kernel(const double* __restrict_
     const double mean = s / nonas;
     double q = 0.0;
     for (int64_t j = 2 * lane; j < N; j += 128) {
-        const v2d x = ld2(col + j);
+        const v2d x = widen(ldx<false>(col + j));
         const double a = x.x - mean;
         q += a * a;
         if (j + 1 < N) {
@@ -1295,33 +1411,108 @@ __global__ __launch_bounds__(kBlock) void stats_kernel(const double* __restrict_
     }
 }
 
-hipError_t marker_stats(const double* X, int64_t ld, int64_t N, int64_t M, double nonas, double alpha_scale,
-                        double* mave, double* msig, hipStream_t st) {
-    if (M <= 0) return hipSuccess;
-    hipLaunchKernelGGL(stats_kernel, dim3((unsigned)cdiv(M, 4)), dim3(kBlock), 0, st, X, ld, N, M, nonas, alpha_scale,
-                       mave, msig);
+__global__ __launch_bounds__(kBlock) void stats_kernel(const double* __restrict__ X, int64_t ld, int64_t N, int64_t M,
+                                                       double nonas, double alpha_scale, double* __restrict__ mave,
+                                                       double* __restrict__ msig) {
+    stats_body(X, ld, N, M, nonas, alpha_scale, mave, msig);
+}
+
+__global__ __launch_bounds__(kBlock) void stats_kernel_f32(const float* __restrict__ X, int64_t ld, int64_t N,
+                                                           int64_t M, double nonas, double alpha_scale,
+                                                           double* __restrict__ mave, double* __restrict__ msig) {
+    stats_body(X, ld, N, M, nonas, alpha_scale, mave, msig);
+}
+
+hipError_t marker_stats(const Shard& s, double nonas, double alpha_scale, double* mave, double* msig,
+                        hipStream_t st) {
+    if (s.M <= 0) return hipSuccess;
+    if (s.f32)
+        hipLaunchKernelGGL(stats_kernel_f32, dim3((unsigned)cdiv(s.M, 4)), dim3(kBlock), 0, st, s.x32(), s.ld, s.N,
+                           s.M, nonas, alpha_scale, mave, msig);
+    else
+        hipLaunchKernelGGL(stats_kernel, dim3((unsigned)cdiv(s.M, 4)), dim3(kBlock), 0, st, s.x64(), s.ld, s.N, s.M,
+                           nonas, alpha_scale, mave, msig);
     return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------
 // synthetic data
 // ---------------------------------------------------------------------------
-__global__ void gen_kernel(uint64_t seed, int kind, int64_t N, int64_t ld, int64_t S, int64_t M, double* X) {
+// (XE = float: the generator's value rounded to nearest even, as an ingest of
+// the fp64 matrix would store it)
+template <class XE>
+__device__ __forceinline__ void gen_body(uint64_t seed, int kind, int64_t N, int64_t ld, int64_t S, int64_t M,
+                                         XE* X) {
     const int64_t total = M * ld;
     for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += (int64_t)gridDim.x * kBlock) {
         const int64_t i = e / ld, j = e - i * ld;
         double v = 0.0;
         if (j < N) v = kind == 1 ? meth_dyadic(seed, S + i, j) : gauss_dyadic(seed, S + i, j);
-        X[e] = v;
+        X[e] = (XE)v;
     }
 }
 
-hipError_t gen_markers(uint64_t seed, int kind, int64_t N, int64_t ld, int64_t S, int64_t M, double* X,
+__global__ void gen_kernel(uint64_t seed, int kind, int64_t N, int64_t ld, int64_t S, int64_t M, double* X) {
+    gen_body(seed, kind, N, ld, S, M, X);
+}
+
+__global__ void gen_kernel_f32(uint64_t seed, int kind, int64_t N, int64_t ld, int64_t S, int64_t M, float* X) {
+    gen_body(seed, kind, N, ld, S, M, X);
+}
+
+hipError_t gen_markers(uint64_t seed, int kind, int64_t N, int64_t ld, int64_t S, int64_t M, void* X, int f32,
                        hipStream_t st) {
     int64_t blocks = cdiv(M * ld, kBlock);
     if (blocks > 65536) blocks = 65536;
     if (blocks < 1) return hipSuccess;
-    hipLaunchKernelGGL(gen_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, seed, kind, N, ld, S, M, X);
+    if (f32)
+        hipLaunchKernelGGL(gen_kernel_f32, dim3((unsigned)blocks), dim3(kBlock), 0, st, seed, kind, N, ld, S, M,
+                           static_cast<float*>(X));
+    else
+        hipLaunchKernelGGL(gen_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, seed, kind, N, ld, S, M,
+                           static_cast<double*>(X));
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// fp32 storage: ingest and read-back conversions
+// ---------------------------------------------------------------------------
+// dst[c*ldd + j] = (float)src[c*lds + j], j < N, c < ncols: a staged chunk of
+// doubles rounded to nearest even into the padded column layout
+__global__ __launch_bounds__(kBlock) void narrow_kernel(const double* __restrict__ src, int64_t lds, int64_t N,
+                                                        int64_t ncols, float* __restrict__ dst, int64_t ldd) {
+    const int64_t total = N * ncols;
+    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += (int64_t)gridDim.x * kBlock) {
+        const int64_t c = e / N, j = e - c * N;
+        dst[c * ldd + j] = (float)src[c * lds + j];
+    }
+}
+
+// dst[c*ldd + j] = (double)src[c*lds + j]: the stored floats widened (exact)
+__global__ __launch_bounds__(kBlock) void widen_kernel(const float* __restrict__ src, int64_t lds, int64_t N,
+                                                       int64_t ncols, double* __restrict__ dst, int64_t ldd) {
+    const int64_t total = N * ncols;
+    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += (int64_t)gridDim.x * kBlock) {
+        const int64_t c = e / N, j = e - c * N;
+        dst[c * ldd + j] = (double)src[c * lds + j];
+    }
+}
+
+hipError_t narrow_cols(const double* src, int64_t lds, int64_t N, int64_t ncols, float* dst, int64_t ldd,
+                       hipStream_t st) {
+    if (N <= 0 || ncols <= 0) return hipSuccess;
+    if (lds < N || ldd < N) return hipErrorInvalidValue;
+    const int64_t blocks = std::min<int64_t>(cdiv(N * ncols, kBlock), 65536);
+    hipLaunchKernelGGL(narrow_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, src, lds, N, ncols, dst, ldd);
+    return hipGetLastError();
+}
+
+hipError_t widen_cols(const float* src, int64_t lds, int64_t N, int64_t ncols, double* dst, int64_t ldd,
+                      hipStream_t st) {
+    if (N <= 0 || ncols <= 0) return hipSuccess;
+    if (lds < N || ldd < N) return hipErrorInvalidValue;
+    const int64_t blocks = std::min<int64_t>(cdiv(N * ncols, kBlock), 65536);
+    hipLaunchKernelGGL(widen_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, src, lds, N, ncols, dst, ldd);
     return hipGetLastError();
 }
 
@@ -2504,16 +2695,17 @@ hipError_t probit_p1(uint64_t seed, int64_t N, double* p1, hipStream_t st) {
 // of a zero quotient can differ, which no sum can see.  Every lane adds its
 // samples in increasing order whatever G / UJ are, so all variants give
 // bitwise identical sums.
-template <int G, int UJ, bool FASTDIV>
-__global__ __launch_bounds__(kBlock) void loo_kernel(const double* __restrict__ X, int64_t ld, int64_t N, int64_t M,
-                                                     const double* __restrict__ ymod, const double* __restrict__ x1,
-                                                     double sqrtN, double* __restrict__ stats) {
+// (the body of loo_kernel and loo_kernel_f32: XE is X's element type)
+template <int G, int UJ, bool FASTDIV, class XE>
+__device__ __forceinline__ void loo_body(const XE* __restrict__ X, int64_t ld, int64_t N, int64_t M,
+                                         const double* __restrict__ ymod, const double* __restrict__ x1,
+                                         double sqrtN, double* __restrict__ stats) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t m0 = ((int64_t)blockIdx.x * (blockDim.x >> 6) + wave) * G;
     const double rinv = 1.0 / sqrtN;
     double acc[G][5];
     double xj[G];
-    const double* col[G];
+    const XE* col[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         const int64_t m = (m0 + g < M) ? m0 + g : M - 1;  // clamp: in-bounds, discarded
@@ -2539,30 +2731,31 @@ __global__ __launch_bounds__(kBlock) void loo_kernel(const double* __restrict__ 
     };
     int64_t j = 2 * lane;
     for (; j + 128 * (UJ - 1) < N; j += 128 * UJ) {
-        v2d yy[UJ], xx[UJ][G];
+        v2d yy[UJ];
+        xpair_t<XE> xx[UJ][G];
 #pragma unroll
         for (int t = 0; t < UJ; ++t)
 #pragma unroll
-            for (int g = 0; g < G; ++g) xx[t][g] = ld_stream(col[g] + j + 128 * t);
+            for (int g = 0; g < G; ++g) xx[t][g] = ldx<true>(col[g] + j + 128 * t);
 #pragma unroll
         for (int t = 0; t < UJ; ++t) yy[t] = ld2(ymod + j + 128 * t);
 #pragma unroll
         for (int g = 0; g < G; ++g)
 #pragma unroll
             for (int t = 0; t < UJ; ++t) {
-                add(g, xx[t][g].x, yy[t].x);
-                add(g, xx[t][g].y, yy[t].y);
+                add(g, widen(xx[t][g]).x, yy[t].x);
+                add(g, widen(xx[t][g]).y, yy[t].y);
             }
     }
     for (; j < N; j += 128) {
-        v2d xx[G];
+        xpair_t<XE> xx[G];
 #pragma unroll
-        for (int g = 0; g < G; ++g) xx[g] = ld_stream(col[g] + j);
+        for (int g = 0; g < G; ++g) xx[g] = ldx<true>(col[g] + j);
         const v2d yy = ld2(ymod + j);
 #pragma unroll
         for (int g = 0; g < G; ++g) {
-            add(g, xx[g].x, yy.x);
-            add(g, xx[g].y, yy.y);
+            add(g, widen(xx[g]).x, yy.x);
+            add(g, widen(xx[g]).y, yy.y);
         }
     }
 #pragma unroll
@@ -2574,22 +2767,37 @@ __global__ __launch_bounds__(kBlock) void loo_kernel(const double* __restrict__ 
         }
 }
 
+template <int G, int UJ, bool FASTDIV>
+__global__ __launch_bounds__(kBlock) void loo_kernel(const double* __restrict__ X, int64_t ld, int64_t N, int64_t M,
+                                                     const double* __restrict__ ymod, const double* __restrict__ x1,
+                                                     double sqrtN, double* __restrict__ stats) {
+    loo_body<G, UJ, FASTDIV>(X, ld, N, M, ymod, x1, sqrtN, stats);
+}
+
+template <int G, int UJ, bool FASTDIV>
+__global__ __launch_bounds__(kBlock) void loo_kernel_f32(const float* __restrict__ X, int64_t ld, int64_t N,
+                                                         int64_t M, const double* __restrict__ ymod,
+                                                         const double* __restrict__ x1, double sqrtN,
+                                                         double* __restrict__ stats) {
+    loo_body<G, UJ, FASTDIV>(X, ld, N, M, ymod, x1, sqrtN, stats);
+}
+
 // The same sums with W waves of a workgroup sharing its G markers: wave w,
 // lane l takes rows 2l + 128 (w + W t), so one load round of the workgroup
 // reads W KiB contiguous of each column (the wave-per-marker form above reads
 // 1 KiB per wave from columns all over the shard); the W wave sums meet in
 // LDS and are added in wave order.
-template <int G, int UJ, int W>
-__global__ __launch_bounds__(64 * W) void loo_wg_kernel(const double* __restrict__ X, int64_t ld, int64_t N, int64_t M,
-                                                        const double* __restrict__ ymod, const double* __restrict__ x1,
-                                                        double sqrtN, double* __restrict__ stats) {
+template <int G, int UJ, int W, class XE>
+__device__ __forceinline__ void loo_wg_body(const XE* __restrict__ X, int64_t ld, int64_t N, int64_t M,
+                                            const double* __restrict__ ymod, const double* __restrict__ x1,
+                                            double sqrtN, double* __restrict__ stats) {
     __shared__ double part[W][5 * G];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t m0 = (int64_t)blockIdx.x * G;
     const double rinv = 1.0 / sqrtN;
     double acc[G][5];
     double xj[G];
-    const double* col[G];
+    const XE* col[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         const int64_t m = (m0 + g < M) ? m0 + g : M - 1;  // clamp: in-bounds, discarded
@@ -2611,30 +2819,31 @@ __global__ __launch_bounds__(64 * W) void loo_wg_kernel(const double* __restrict
     constexpr int64_t RS = 128 * W;  // rows per load round of the workgroup
     int64_t j = 2 * lane + 128 * wave;
     for (; j + RS * (UJ - 1) < N; j += RS * UJ) {
-        v2d yy[UJ], xx[UJ][G];
+        v2d yy[UJ];
+        xpair_t<XE> xx[UJ][G];
 #pragma unroll
         for (int t = 0; t < UJ; ++t)
 #pragma unroll
-            for (int g = 0; g < G; ++g) xx[t][g] = ld_stream(col[g] + j + RS * t);
+            for (int g = 0; g < G; ++g) xx[t][g] = ldx<true>(col[g] + j + RS * t);
 #pragma unroll
         for (int t = 0; t < UJ; ++t) yy[t] = ld2(ymod + j + RS * t);
 #pragma unroll
         for (int g = 0; g < G; ++g)
 #pragma unroll
             for (int t = 0; t < UJ; ++t) {
-                add(g, xx[t][g].x, yy[t].x);
-                add(g, xx[t][g].y, yy[t].y);
+                add(g, widen(xx[t][g]).x, yy[t].x);
+                add(g, widen(xx[t][g]).y, yy[t].y);
             }
     }
     for (; j < N; j += RS) {  // (N even or the pad row: ld-padded columns, zero pads)
-        v2d xx[G];
+        xpair_t<XE> xx[G];
 #pragma unroll
-        for (int g = 0; g < G; ++g) xx[g] = ld_stream(col[g] + j);
+        for (int g = 0; g < G; ++g) xx[g] = ldx<true>(col[g] + j);
         const v2d yy = ld2(ymod + j);
 #pragma unroll
         for (int g = 0; g < G; ++g) {
-            add(g, xx[g].x, yy.x);
-            add(g, xx[g].y, yy.y);
+            add(g, widen(xx[g]).x, yy.x);
+            add(g, widen(xx[g]).y, yy.y);
         }
     }
 #pragma unroll
@@ -2653,6 +2862,21 @@ __global__ __launch_bounds__(64 * W) void loo_wg_kernel(const double* __restrict
     }
 }
 
+template <int G, int UJ, int W>
+__global__ __launch_bounds__(64 * W) void loo_wg_kernel(const double* __restrict__ X, int64_t ld, int64_t N, int64_t M,
+                                                        const double* __restrict__ ymod, const double* __restrict__ x1,
+                                                        double sqrtN, double* __restrict__ stats) {
+    loo_wg_body<G, UJ, W>(X, ld, N, M, ymod, x1, sqrtN, stats);
+}
+
+template <int G, int UJ, int W>
+__global__ __launch_bounds__(64 * W) void loo_wg_kernel_f32(const float* __restrict__ X, int64_t ld, int64_t N,
+                                                            int64_t M, const double* __restrict__ ymod,
+                                                            const double* __restrict__ x1, double sqrtN,
+                                                            double* __restrict__ stats) {
+    loo_wg_body<G, UJ, W>(X, ld, N, M, ymod, x1, sqrtN, stats);
+}
+
 struct LooVariant { int G, UJ; bool FD; int W = 0; };  // W > 0: loo_wg_kernel
 static constexpr LooVariant kLooVariants[] = {
     {4, 2, true}, {4, 2, false}, {2, 2, true}, {8, 1, true}, {4, 1, true}, {4, 4, true}, {2, 4, true}, {8, 2, true},
@@ -2667,13 +2891,14 @@ static constexpr int kNumLooVariants = sizeof(kLooVariants) / sizeof(kLooVariant
 int loo_variant_count() { return kNumLooVariants; }
 bool loo_variant_ok(int v) { return v >= 0 && v < kNumLooVariants; }
 
-std::string loo_kernel_name(int variant) {
+std::string loo_kernel_name(int variant, int f32) {
     const LooVariant& v = kLooVariants[loo_variant_ok(variant) ? variant : kLooDefault];
+    const char* sfx = f32 ? "_f32" : "";
     char b[64];
     if (v.W > 0)
-        std::snprintf(b, sizeof b, "loo_wg_kernel<%d, %d, %d>", v.G, v.UJ, v.W);
+        std::snprintf(b, sizeof b, "loo_wg_kernel%s<%d, %d, %d>", sfx, v.G, v.UJ, v.W);
     else
-        std::snprintf(b, sizeof b, "loo_kernel<%d, %d, %s>", v.G, v.UJ, v.FD ? "true" : "false");
+        std::snprintf(b, sizeof b, "loo_kernel%s<%d, %d, %s>", sfx, v.G, v.UJ, v.FD ? "true" : "false");
     return b;
 }
 
@@ -2683,15 +2908,23 @@ static void launch_loo(const Shard& s, const double* ymod, const double* x1, dou
     // two waves per workgroup, as A^T.u (C5 shape: 7339 vs 7477 us with four);
     // VAMPOMI_LOO_WPB: tuning experiments
     static const int wpb = std::getenv("VAMPOMI_LOO_WPB") ? std::max(1, std::min(4, std::atoi(std::getenv("VAMPOMI_LOO_WPB")))) : 2;
-    hipExtLaunchKernelGGL((loo_kernel<G, UJ, FD>), dim3((unsigned)cdiv(s.M, wpb * G)), dim3(64 * wpb), 0, st, tm.start,
-                          tm.stop, 0, s.X, s.ld, s.N, s.M, ymod, x1, sqrtN, stats);
+    if (s.f32)
+        hipExtLaunchKernelGGL((loo_kernel_f32<G, UJ, FD>), dim3((unsigned)cdiv(s.M, wpb * G)), dim3(64 * wpb), 0, st,
+                              tm.start, tm.stop, 0, s.x32(), s.ld, s.N, s.M, ymod, x1, sqrtN, stats);
+    else
+        hipExtLaunchKernelGGL((loo_kernel<G, UJ, FD>), dim3((unsigned)cdiv(s.M, wpb * G)), dim3(64 * wpb), 0, st,
+                              tm.start, tm.stop, 0, s.x64(), s.ld, s.N, s.M, ymod, x1, sqrtN, stats);
 }
 
 template <int G, int UJ, int W>
 static void launch_loo_wg(const Shard& s, const double* ymod, const double* x1, double sqrtN, double* stats,
                           hipStream_t st, const Timing& tm) {
-    hipExtLaunchKernelGGL((loo_wg_kernel<G, UJ, W>), dim3((unsigned)cdiv(s.M, G)), dim3(64 * W), 0, st, tm.start,
-                          tm.stop, 0, s.X, s.ld, s.N, s.M, ymod, x1, sqrtN, stats);
+    if (s.f32)
+        hipExtLaunchKernelGGL((loo_wg_kernel_f32<G, UJ, W>), dim3((unsigned)cdiv(s.M, G)), dim3(64 * W), 0, st,
+                              tm.start, tm.stop, 0, s.x32(), s.ld, s.N, s.M, ymod, x1, sqrtN, stats);
+    else
+        hipExtLaunchKernelGGL((loo_wg_kernel<G, UJ, W>), dim3((unsigned)cdiv(s.M, G)), dim3(64 * W), 0, st, tm.start,
+                              tm.stop, 0, s.x64(), s.ld, s.N, s.M, ymod, x1, sqrtN, stats);
 }
 
 hipError_t loo_sums(const Shard& s, const double* ymod, const double* x1, double sqrtN, double* stats,

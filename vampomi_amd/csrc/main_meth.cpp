@@ -195,6 +195,10 @@ int main(int argc, char** argv) {
     vampomi_ctx* ctx = nullptr;
     if (vampomi_open(&d, &ctx) != VAMPOMI_OK) return die("cannot open the device context");
     g_ctx = ctx;
+    // (without the flag the context keeps its default, VAMPOMI_STORAGE included)
+    if (opt.meth_storage_set &&
+        vampomi_set_storage(ctx, opt.meth_storage == "f32" ? VAMPOMI_STORE_F32 : VAMPOMI_STORE_F64) != VAMPOMI_OK)
+        return die("methylation storage");
     // every rank has joined the communicator (its init is collective): the
     // rendezvous file has served and must not be read by a later job
     if (rank == 0 && !rdzv_path.empty()) vio::rdzv_remove(rdzv_path);
@@ -207,7 +211,9 @@ int main(int argc, char** argv) {
     const std::string& meth = test_mode ? opt.meth_file_test : opt.meth_file;
     if (vampomi_read_phen(ctx, phen.c_str(), standardize) != VAMPOMI_OK) return die("phenotype");
     if (rank == 0) std::cout << "meth file name = " << meth << std::endl;
-    if (vampomi_load_meth_file(ctx, meth.c_str()) != VAMPOMI_OK) return die("methylation data");
+    if ((opt.meth_dtype == "f32" ? vampomi_load_meth_file_f32(ctx, meth.c_str())
+                                 : vampomi_load_meth_file(ctx, meth.c_str())) != VAMPOMI_OK)
+        return die("methylation data");
     // the ranks' shards load at their own pace (one rank's file may come off
     // slower storage): they meet here under a limit of their own, so the
     // first collective of the run is not the one that waits for the slowest

@@ -68,6 +68,8 @@ bool parse(int argc, char** argv, Options& o, std::string& echo) {
         // engine extensions
         {"--seed", {Kind::Str, nullptr, nullptr}},
         {"--batch-rhs", {Kind::Int, &o.batch_rhs, nullptr}},
+        {"--meth-storage", {Kind::Str, &o.meth_storage, nullptr}},
+        {"--meth-dtype", {Kind::Str, &o.meth_dtype, nullptr}},
     };
     std::stringstream ss;
     ss << "\nardyh command line options:\n";
@@ -87,6 +89,13 @@ bool parse(int argc, char** argv, Options& o, std::string& echo) {
         const Flag& fl = f->second;
         switch (fl.kind) {
             case Kind::Str:
+                if ((name == "--meth-storage" || name == "--meth-dtype") && std::strcmp(val, "f64") != 0 &&
+                    std::strcmp(val, "f32") != 0) {
+                    std::cout << "FATAL  : option " << name << " has to be f64 or f32! (" << val << " was passed)"
+                              << std::endl;
+                    return false;
+                }
+                if (name == "--meth-storage") o.meth_storage_set = true;
                 if (name == "--seed")
                     o.seed = std::strtoull(val, nullptr, 0);
                 else

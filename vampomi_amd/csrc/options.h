@@ -25,6 +25,10 @@ struct Options {
     // engine extensions (not in the reference): Bernoulli seed, RHS batching
     unsigned long long seed = 0x5EED5EEDULL;
     int batch_rhs = 4;
+    // how the methylation shard is held on the device (--meth-storage) and the
+    // element type of --meth-file / --meth-file-test (--meth-dtype): f64 | f32
+    std::string meth_storage = "f64", meth_dtype = "f64";
+    bool meth_storage_set = false;  // --meth-storage was given (else the context's default stands)
 };
 
 // Parses argv exactly like Options::read_command_line_options + check_options:
