@@ -21,7 +21,10 @@
  *   vamp::g1 / vamp::g1d       src/vamp.cpp:440-492     -> vampomi_denoise  (COLLECTIVE: alpha1 sum)
  *   vamp::updatePrior          src/vamp.cpp:531-643     -> vampomi_update_prior (COLLECTIVE)
  *   vamp::g1_bin_class / g1d_bin_class
- *        src/vamp_probit.cpp:469-488                    -> vampomi_denoise_bin
+ *        src/vamp_probit.cpp:469-488                    -> vampomi_denoise_bin / _denoise_bin_cov
+ *   data::read_covariates      src/data.cpp:159-227     -> vampomi_read_covariates / vampomi_set_covariates
+ *   vamp::Newton_method_cov / grad_cov / mlogL_probit
+ *        src/vamp_probit.cpp:490-617                    -> vampomi_newton_cov / vampomi_cov_eval
  *   vamp::vamp + vamp::infere / infere_linear / infere_bin_class
  *        src/vamp.cpp:18-91, 94-107, 110-438,
  *        src/vamp_probit.cpp:19-488                     -> vampomi_infere   (COLLECTIVE)
@@ -51,6 +54,7 @@ extern "C" {
 
 #define VAMPOMI_ABI_VERSION 3
 #define VAMPOMI_MAX_L 64          /* mixture components */
+#define VAMPOMI_MAX_C 64          /* covariates of the probit model */
 #define VAMPOMI_UNIQUE_ID_BYTES 128
 
 typedef enum {
@@ -165,6 +169,58 @@ vampomi_status vampomi_simulate_phen(vampomi_ctx* ctx, uint64_t seed, double lam
  * src/data.cpp:40-41). COLLECTIVE */
 vampomi_status vampomi_simulate_phen_binary(vampomi_ctx* ctx, uint64_t seed, double lam, double h2,
                                             double* beta_out);
+/* ---- covariates of the probit model (data::read_covariates, src/data.cpp:159-227) ----
+ * An N x C table (age, sex, batch, cell types ...), held whole on every rank as
+ * y is.  A context that holds one (C > 0) fits the covariate effects at the
+ * start of every bin_class run and offsets the z-side denoiser with them
+ * (below); the LINEAR model ignores the table, as the reference's main_meth.exe
+ * does.  Two properties of the reference's fit that are kept: a constant column
+ * standardises to zeros and makes the Newton matrix singular, so the fit
+ * returns ALL effects zero; and no intercept is fitted unless the table
+ * carries a (non-constant) column for one.
+ *
+ * vampomi_parse_covariates needs no device: the file's first line (a header) is
+ * skipped; every further line is split on whitespace runs, its first two fields
+ * (the IDs) skipped, and exactly C numeric fields must remain, else the
+ * reference's "FATAL: number of covariates = ... does not match ..." line is
+ * printed to stdout and the call returns VAMPOMI_ERR_IO (the reference exits);
+ * a row count other than N is VAMPOMI_ERR_IO too.  standardize: per column,
+ * accumulated in long double, the mean and the POPULATION standard deviation
+ * (divided by N); a column with deviation < 1e-8 becomes zeros, any other
+ * (v - mean)/deviation.  out: C columns of N doubles (covariate-major).
+ * C == 0 does nothing; C > VAMPOMI_MAX_C is VAMPOMI_ERR_ARG. */
+vampomi_status vampomi_parse_covariates(const char* path, int64_t N, int C, int standardize, double* out);
+/* the file, standardised as the reference always does, into the context (C == 0: none) */
+vampomi_status vampomi_read_covariates(vampomi_ctx* ctx, const char* path, int C);
+/* host table: C columns of N samples, column stride ld_in >= N (C == 0: none) */
+vampomi_status vampomi_set_covariates(vampomi_ctx* ctx, const double* Z, int C, int64_t ld_in, int standardize);
+/* the stored columns, C x N doubles, covariate-major (host) */
+vampomi_status vampomi_get_covariates(vampomi_ctx* ctx, double* out);
+/* One evaluation of the Newton quantities (src/vamp_probit.cpp:536-551, 490-523)
+ * at eta (C, host) with the genetic predictor gg (N, `mem`; NULL = zeros): per
+ * sample g = gg_i + sum_j Z_ij eta_j, s = 2 y_i - 1, arg = s g, ratio =
+ * (2/sqrt(2 pi)) / erfcx(-arg/sqrt 2), lambda = ratio s, w = lambda (lambda + g);
+ * H_jk = sum_i Z_ij Z_ik w (C*C, host), rhs_j = sum_i Z_ij lambda (C, host; the
+ * gradient of -logL/N is -rhs/N), *mlogL = -(1/N) sum_i log Phi(arg).  Every sum
+ * runs in a fixed order that depends on neither the device nor the launch: the
+ * results repeat bit for bit.  H, rhs, mlogL may each be NULL.  Rank-local. */
+vampomi_status vampomi_cov_eval(vampomi_ctx* ctx, const double* gg, const double* eta, double* H, double* rhs,
+                                double* mlogL, int mem);
+/* vamp::Newton_method_cov (:525-617): up to 501 Newton steps from eta0 (C, host;
+ * NULL = zeros), H factored by LU with partial pivoting (a zero pivot: no step),
+ * a backtracking line search (scale 1, x0.9, at most 299 evaluations; accepted
+ * when mlogL(eta + d) <= mlogL(eta) + d.grad/2); rel_err = |eta - eta_new|/|eta|
+ * (1 when |eta| = 0) below 1e-4 stops BEFORE eta takes the step (the last step
+ * is discarded, as in the reference), a rise of mlogL stops after it.  eta (C,
+ * host) receives the effects, *iters the outer iterations run; backtracks and
+ * rel_err (each NULL or >= 501 entries) one value per outer iteration.
+ * Rank-local: the N-side is replicated, every rank computes the same bits. */
+vampomi_status vampomi_newton_cov(vampomi_ctx* ctx, const double* gg, const double* eta0, double* eta, int* iters,
+                                  int* backtracks, double* rel_err, int mem);
+/* the effects fitted by the last vampomi_vamp_begin / vampomi_infere of a
+ * bin_class run on this context (C doubles; nothing when it holds no
+ * covariates); VAMPOMI_ERR_STATE before that */
+vampomi_status vampomi_get_cov_eff(vampomi_ctx* ctx, double* out);
 /* (the statistics of the STORED values, accumulated in fp64) */
 vampomi_status vampomi_get_marker_stats(vampomi_ctx* ctx, double* mave, double* msig);
 /* copy local markers [i0, i0+count) back to the host, count x N doubles
@@ -202,10 +258,16 @@ vampomi_status vampomi_update_prior(vampomi_ctx* ctx, const double* r1, double g
 
 /* probit z-denoiser: z1[i] = g1_bin_class(p1[i], tau1, y[i]) with the context's
  * phenotype y (raw 0/1), *sum_d = sum_i g1d_bin_class(p1[i], tau1, y[i]) (local:
- * the N-side is replicated on every rank).  probit_var = 1, no covariates.
+ * the N-side is replicated on every rank).  probit_var = 1, covariate offset 0
+ * (vampomi_denoise_bin_cov with m_cov = NULL).
  * src/vamp_probit.cpp:213-233, 469-488; erfcx src/utilities.cpp:293-363 */
 vampomi_status vampomi_denoise_bin(vampomi_ctx* ctx, const double* p1, double tau1, double* z1,
                                    double* sum_d, int mem);
+/* the same with the covariate offsets m_cov (N, `mem`; m_cov_i = Z_i.cov_eff,
+ * :213-233): g1 / g1d_bin_class(p1[i], tau1, y[i], m_cov[i]), i.e. c = (p1 +
+ * m_cov)/sqrt(1 + 1/tau1).  m_cov = NULL: vampomi_denoise_bin, bit for bit */
+vampomi_status vampomi_denoise_bin_cov(vampomi_ctx* ctx, const double* p1, double tau1, const double* m_cov,
+                                       double* z1, double* sum_d, int mem);
 
 /* ---- the VAMP linear and probit models (vamp::infere) ---- */
 typedef struct {
@@ -241,7 +303,9 @@ typedef struct {
     const char* model;            /* "linear" (NULL == "linear") or "bin_class" (probit,
                                      src/vamp_probit.cpp; phenotype must be raw 0/1, i.e. read
                                      with standardize = 0; h2/gamw unused; seed also keys the
-                                     Gaussian start p1) */
+                                     Gaussian start p1; the context's covariates, if any, are
+                                     fitted at vampomi_vamp_begin and offset the z-side
+                                     denoiser; "linear" ignores them) */
 } vampomi_params;
 
 typedef struct {
@@ -274,6 +338,11 @@ vampomi_status vampomi_infere(vampomi_ctx* ctx, const vampomi_params* p, vampomi
 vampomi_status vampomi_vamp_begin(vampomi_ctx* ctx, const vampomi_params* p, vampomi_result* r);
 vampomi_status vampomi_vamp_step(vampomi_ctx* ctx, int* stopped);
 vampomi_status vampomi_vamp_end(vampomi_ctx* ctx);
+/* Between vampomi_vamp_begin and vampomi_vamp_end of a bin_class run: the p1
+ * (N, host; may be NULL) and tau1 that the NEXT vampomi_vamp_step's z-side
+ * denoiser reads (whether that step queues it or the previous one did).
+ * VAMPOMI_ERR_STATE otherwise. */
+vampomi_status vampomi_get_probit_state(vampomi_ctx* ctx, double* p1, double* tau1);
 /* the last step's phase times as the host sees them (rank-local wall clock),
  * replacing the reference's per-iteration stopwatches "CG took" / "onsager
  * took" (src/vamp.cpp:313-316, :326-333; one interval here: both solves share

@@ -80,6 +80,7 @@ class Data:
         check(self._lib.vampomi_open(C.byref(d), C.byref(h)))
         self.ctx = h
         self.N, self.Mt, self.rank, self.nranks = N, Mt, rank, nranks
+        self.C = 0  # covariates held (set_covariates / read_covariates)
         M, S, ld = C.c_int64(), C.c_int64(), C.c_int64()
         check(self._lib.vampomi_shard_info(self.ctx, C.byref(M), C.byref(S), C.byref(ld)))
         self.M, self.S, self.ld = M.value, S.value, ld.value
@@ -148,6 +149,60 @@ class Data:
         if y.shape != (self.N,):
             raise ValueError("phenotype must have N entries")
         check(self._lib.vampomi_set_phen(self.ctx, _dp(y), 1 if standardize else 0))
+
+    # -- covariates of the probit model (data::read_covariates, src/data.cpp:159-227) --
+    def read_covariates(self, path: str, C: int):
+        """Header line, then per row two IDs and C numbers; standardised per
+        column (population deviation; a constant column becomes zeros)."""
+        check(self._lib.vampomi_read_covariates(self.ctx, path.encode(), C))
+        self.C = C
+
+    def set_covariates(self, Z: Optional[np.ndarray], standardize: bool = True):
+        """Z: (N, C), one row per sample (None or C == 0: no covariates)."""
+        if Z is None or np.size(Z) == 0:
+            check(self._lib.vampomi_set_covariates(self.ctx, None, 0, self.N, 0))
+            self.C = 0
+            return
+        Z = np.asarray(Z, dtype=np.float64)
+        if Z.ndim != 2 or Z.shape[0] != self.N:
+            raise ValueError("covariates must be an (N, C) array")
+        Zt = np.ascontiguousarray(Z.T)  # covariate-major
+        check(self._lib.vampomi_set_covariates(self.ctx, _dp(Zt), Z.shape[1], self.N, 1 if standardize else 0))
+        self.C = Z.shape[1]
+
+    def get_covariates(self) -> np.ndarray:
+        """The stored (standardised) table, (N, C)."""
+        C_ = getattr(self, "C", 0)
+        out = np.zeros((max(C_, 1), self.N))
+        check(self._lib.vampomi_get_covariates(self.ctx, _dp(out)))
+        return np.ascontiguousarray(out[:C_].T)
+
+    def cov_eval(self, eta: np.ndarray, gg: Optional[np.ndarray] = None):
+        """One evaluation of Newton_method_cov's sums (src/vamp_probit.cpp:536-551):
+        (H (C, C), rhs (C), mlogL) at eta with the genetic predictor gg (None: zeros)."""
+        C_ = getattr(self, "C", 0)
+        eta = np.ascontiguousarray(eta, dtype=np.float64)
+        if eta.shape != (C_,):
+            raise ValueError("eta must have C entries")
+        g = None if gg is None else np.ascontiguousarray(gg, dtype=np.float64)
+        H, rhs, ml = np.zeros((max(C_, 1), max(C_, 1))), np.zeros(max(C_, 1)), C.c_double()
+        check(self._lib.vampomi_cov_eval(self.ctx, None if g is None else _dp(g), _dp(eta), _dp(H), _dp(rhs),
+                                         C.byref(ml), MEM_HOST))
+        return H[:C_, :C_], rhs[:C_], ml.value
+
+    def newton_cov(self, gg: Optional[np.ndarray] = None, eta0: Optional[np.ndarray] = None):
+        """vamp::Newton_method_cov (:525-617): (eta, outer iterations, backtracks
+        per iteration, rel_err per iteration)."""
+        C_ = getattr(self, "C", 0)
+        g = None if gg is None else np.ascontiguousarray(gg, dtype=np.float64)
+        e0 = None if eta0 is None else np.ascontiguousarray(eta0, dtype=np.float64)
+        eta = np.zeros(max(C_, 1))
+        it = C.c_int()
+        bt = np.zeros(501, dtype=np.int32)
+        rel = np.zeros(501)
+        check(self._lib.vampomi_newton_cov(self.ctx, None if g is None else _dp(g), None if e0 is None else _dp(e0),
+                                           _dp(eta), C.byref(it), _dp(bt), _dp(rel), MEM_HOST))
+        return eta[:C_], it.value, bt[: it.value].copy(), rel[: it.value].copy()
 
     def simulate_phen_binary(self, seed: int, lam: float = 0.1, h2: float = 0.8) -> np.ndarray:
         """Liability of simulate_phen thresholded at 0, stored raw (bin_class); returns beta."""
@@ -257,12 +312,19 @@ class Data:
                                              EM_err_thr, learn_vars, merge_vars_thr, MEM_HOST))
         return pr[: L.value].copy(), va_[: L.value].copy()
 
-    def denoise_bin(self, p1: np.ndarray, tau1: float):
-        """g1_bin_class / g1d_bin_class over the phenotype (src/vamp_probit.cpp:469-488): (z1, sum of g1d)."""
+    def denoise_bin(self, p1: np.ndarray, tau1: float, m_cov: Optional[np.ndarray] = None):
+        """g1_bin_class / g1d_bin_class over the phenotype (src/vamp_probit.cpp:469-488): (z1, sum of g1d);
+        m_cov (N): the covariate offsets Z_i.cov_eff (None: zero, the kernel without an offset)."""
         p1 = np.ascontiguousarray(p1, dtype=np.float64)
         z = np.zeros(self.N)
         sd = C.c_double()
-        check(self._lib.vampomi_denoise_bin(self.ctx, _dp(p1), tau1, _dp(z), C.byref(sd), MEM_HOST))
+        if m_cov is None:
+            check(self._lib.vampomi_denoise_bin(self.ctx, _dp(p1), tau1, _dp(z), C.byref(sd), MEM_HOST))
+        else:
+            m = np.ascontiguousarray(m_cov, dtype=np.float64)
+            if m.shape != (self.N,):
+                raise ValueError("m_cov must have N entries")
+            check(self._lib.vampomi_denoise_bin_cov(self.ctx, _dp(p1), tau1, _dp(m), _dp(z), C.byref(sd), MEM_HOST))
         return z, sd.value
 
     def denoise(self, r1: np.ndarray, gam1: float, probs: Sequence[float], vars_scaled: Sequence[float]):
@@ -468,6 +530,22 @@ class Vamp:
         check(load().vampomi_vamp_end(self.data.ctx))
         self._active = False
         return self.x1_final[: self.data.M].copy()
+
+    @property
+    def cov_eff(self) -> np.ndarray:
+        """The covariate effects fitted at the start of this context's last
+        bin_class run (C entries; empty without covariates)."""
+        C_ = getattr(self.data, "C", 0)
+        out = np.zeros(max(C_, 1))
+        check(load().vampomi_get_cov_eff(self.data.ctx, _dp(out)))
+        return out[:C_]
+
+    def probit_state(self):
+        """(p1 (N), tau1) that the next step's z-side denoiser reads (bin_class, between begin and end)."""
+        p1 = np.zeros(self.data.N)
+        t = C.c_double()
+        check(load().vampomi_get_probit_state(self.data.ctx, _dp(p1), C.byref(t)))
+        return p1, t.value
 
     @property
     def iterations_run(self) -> int:

@@ -24,6 +24,7 @@ LIB_PATH = os.environ.get("VAMPOMI_LIB") or os.path.join(HERE, "lib", "libvampom
 CLI_PATH = os.path.join(HERE, "bin", "main_meth.exe")
 
 MAX_L = 64
+MAX_C = 64
 UNIQUE_ID_BYTES = 128
 MEM_HOST, MEM_DEVICE = 0, 1
 GEN_GAUSS, GEN_METH = 0, 1
@@ -131,6 +132,15 @@ SIGNATURES = {
     "vampomi_update_prior": (C.c_int, [_P, _P, C.c_double, C.POINTER(C.c_int), _P, _P, C.c_int, C.c_double,
                                         C.c_int, C.c_double, C.c_int]),
     "vampomi_denoise_bin": (C.c_int, [_P, _P, C.c_double, _P, C.POINTER(C.c_double), C.c_int]),
+    "vampomi_denoise_bin_cov": (C.c_int, [_P, _P, C.c_double, _P, _P, C.POINTER(C.c_double), C.c_int]),
+    "vampomi_parse_covariates": (C.c_int, [C.c_char_p, C.c_int64, C.c_int, C.c_int, _P]),
+    "vampomi_read_covariates": (C.c_int, [_P, C.c_char_p, C.c_int]),
+    "vampomi_set_covariates": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int]),
+    "vampomi_get_covariates": (C.c_int, [_P, _P]),
+    "vampomi_cov_eval": (C.c_int, [_P, _P, _P, _P, _P, C.POINTER(C.c_double), C.c_int]),
+    "vampomi_newton_cov": (C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_int), _P, _P, C.c_int]),
+    "vampomi_get_cov_eff": (C.c_int, [_P, _P]),
+    "vampomi_get_probit_state": (C.c_int, [_P, _P, C.POINTER(C.c_double)]),
     "vampomi_denoise": (C.c_int, [_P, _P, C.c_double, _P, _P, C.c_int, _P, _P, C.POINTER(C.c_double), C.c_int]),
     "vampomi_params_default": (None, [C.POINTER(Params)]),
     "vampomi_infere": (C.c_int, [_P, C.POINTER(Params), C.POINTER(Result)]),

@@ -101,6 +101,15 @@ struct vampomi_ctx {
     double* y = nullptr;     // ld, zero pad
     std::vector<double> y_host;
     bool have_X = false, have_y = false;
+    // covariates of the probit model (covariates.cpp): the whole N x C table on
+    // every rank, as y.  cov_host: C columns of N; cov_Z: C columns of stride ld
+    int cov_C = 0;
+    std::vector<double> cov_host;
+    double* cov_Z = nullptr;
+    double* cov_part = nullptr;  // cov_tiles(N) x cov_nq(C) tile partials
+    double* cov_dev = nullptr;   // eta (kCovMaxC), then H, rhs, mlogL of vk::cov_eval
+    std::vector<double> cov_eff;  // fitted by the last vampomi_vamp_begin (bin_class)
+    bool cov_fitted = false;
 
     vk::AxPlan axp{};
     int atx_variant = vk::kAtxDefault, loo_variant = vk::kLooDefault;  // per context (dev hooks)
@@ -413,3 +422,18 @@ vampomi_status op_dev(vampomi_ctx* c, int K, const vk::OpArgs& a, const int* gat
 // COLLECTIVE
 vampomi_status op_dev_plain(vampomi_ctx* c, const vk::OpArgs& a, const double* const* px, double* const* out,
                             const int* gate);
+
+// ---- covariates of the probit model (covariates.cpp) -----------------------------
+// One evaluation of vamp::Newton_method_cov's sums (src/vamp_probit.cpp:536-551)
+// at eta (host, C) with gg (device, N, may be null: zeros): H (C*C), rhs (C) and
+// mlogL to the host (any may be null).  One host wait.
+vampomi_status cov_eval_dev(vampomi_ctx* c, const double* gg, const double* eta, double* H, double* rhs,
+                            double* mlogL);
+// vamp::Newton_method_cov (:525-617) around the device sums, gg as above; eta
+// (host, C) starts at eta0 (null: zeros).  iters: outer iterations run;
+// backtracks / rel_err (may be null, >= 501 entries): per outer iteration.
+// Rank-local: the N-side is replicated, every rank computes the same bits
+vampomi_status cov_newton_dev(vampomi_ctx* c, const double* gg, const double* eta0, double* eta, int* iters,
+                              int* backtracks, double* rel_err);
+// m (device, N) = Z eta for eta on the host
+vampomi_status cov_offset_dev(vampomi_ctx* c, const double* eta, double* m);

@@ -1128,7 +1128,7 @@ void release_ctx_resources(vampomi_ctx* c) {
     if (c->X) (void)hipFree(c->X);
     c->X = nullptr;
     for (double** p : {&c->mave, &c->msig, &c->y, &c->ax_part, &c->red_part, &c->scal, &c->nbuf, &c->mbuf,
-                       &c->op_part, &c->op_nvec})
+                       &c->op_part, &c->op_nvec, &c->cov_Z, &c->cov_part, &c->cov_dev})
         dev_free(*p);
     if (c->op_xg) (void)hipFree(c->op_xg);
     c->op_xg = nullptr;
@@ -1784,23 +1784,33 @@ extern "C" vampomi_status vampomi_denoise(vampomi_ctx* c, const double* r1, doub
     return VAMPOMI_OK;
 }
 
-extern "C" vampomi_status vampomi_denoise_bin(vampomi_ctx* c, const double* p1, double tau1, double* z1,
-                                              double* sum_d, int mem) {
+extern "C" vampomi_status vampomi_denoise_bin_cov(vampomi_ctx* c, const double* p1, double tau1, const double* m_cov,
+                                                  double* z1, double* sum_d, int mem) {
     if (!c || !p1) return fail(VAMPOMI_ERR_ARG, "null argument");
     if (!c->have_y) return fail(VAMPOMI_ERR_STATE, "set the phenotype first");
     HIPCHK(hipSetDevice(c->device));
     double* pin = c->nbuf;
     double* zo = c->nbuf + c->ld;
+    double* mc = c->nbuf + 2 * c->ld;
     STCHK(stage_in(c, p1, c->N, mem, pin));
+    if (m_cov) STCHK(stage_in(c, m_cov, c->N, mem, mc));
     double sd = 0.0;
     DotBatch db(c);
     vk::RedOut ro{};
     STCHK(db.sink(1, false, &sd, &ro));
-    HIPCHK(vk::probit_denoise(c->N, pin, c->y, tau1, zo, ro, c->st));
+    if (m_cov)
+        HIPCHK(vk::probit_denoise_cov(c->N, pin, c->y, mc, tau1, zo, ro, c->st));
+    else
+        HIPCHK(vk::probit_denoise(c->N, pin, c->y, tau1, zo, ro, c->st));
     STCHK(db.flush());
     if (z1) STCHK(stage_out(c, zo, c->N, mem, z1));
     if (sum_d) *sum_d = sd;
     return VAMPOMI_OK;
+}
+
+extern "C" vampomi_status vampomi_denoise_bin(vampomi_ctx* c, const double* p1, double tau1, double* z1,
+                                              double* sum_d, int mem) {
+    return vampomi_denoise_bin_cov(c, p1, tau1, nullptr, z1, sum_d, mem);
 }
 
 // --run-mode association_test --pval-method loo (src/main_meth.cpp:245-264,

@@ -19,34 +19,103 @@ namespace vio {
 
 static bool is_ws(char c) { return c == ' ' || c == '\t' || c == '\r' || c == '\n' || c == '\v' || c == '\f'; }
 
+// std::sregex_token_iterator over "\\s+" with submatch -1: the text between
+// whitespace runs; a leading run gives an empty first token, a trailing one
+// no token
+static void split_ws(const std::string& line, std::vector<std::string>& tok) {
+    tok.clear();
+    size_t i = 0;
+    const size_t n = line.size();
+    for (;;) {
+        size_t j = i;
+        while (j < n && !is_ws(line[j])) ++j;
+        if (j == n) {  // suffix after the last separator: only if non-empty
+            if (j > i || tok.empty()) tok.push_back(line.substr(i, j - i));
+            break;
+        }
+        tok.push_back(line.substr(i, j - i));  // text before a separator (may be empty)
+        while (j < n && is_ws(line[j])) ++j;
+        i = j;
+        if (i == n) break;
+    }
+}
+
 int64_t read_phen(const std::string& path, std::vector<double>& y) {
     std::ifstream in(path);
     if (!in.is_open()) return -1;
     y.clear();
     std::string line;
+    std::vector<std::string> tok;
     while (std::getline(in, line)) {
         // third token of the "\\s+" split with submatch -1: a leading run of
         // whitespace produces an empty first token.
-        std::vector<std::string> tok;
-        size_t i = 0;
-        const size_t n = line.size();
-        for (;;) {
-            size_t j = i;
-            while (j < n && !is_ws(line[j])) ++j;
-            if (j == n) {  // suffix after the last separator: only if non-empty
-                if (j > i || tok.empty()) tok.push_back(line.substr(i, j - i));
-                break;
-            }
-            tok.push_back(line.substr(i, j - i));  // text before a separator (may be empty)
-            while (j < n && is_ws(line[j])) ++j;
-            i = j;
-            if (i == n) break;
-        }
+        split_ws(line, tok);
         if (tok.size() < 3) continue;
         if (tok[2] == "NA") return -2;
         y.push_back(std::atof(tok[2].c_str()));
     }
     return (int64_t)y.size();
+}
+
+void standardize_covariates(double* Z, int64_t N, int C, int64_t ld) {
+    for (int j = 0; j < C; ++j) {  // src/data.cpp:205-226
+        double* col = Z + (int64_t)j * ld;
+        long double cavg = 0.0, csig = 0.0;
+        for (int64_t i = 0; i < N; ++i) cavg += col[i];
+        cavg = cavg / double(N);
+        for (int64_t i = 0; i < N; ++i) csig += ((col[i] - cavg) * (col[i] - cavg));
+        csig = std::sqrt(csig / double(N));
+        for (int64_t i = 0; i < N; ++i) {
+            if (csig < 0.00000001)
+                col[i] = 0;
+            else
+                col[i] = (double)((col[i] - cavg) / csig);
+        }
+    }
+}
+
+int read_covariates(const std::string& path, int64_t N, int C, bool standardize, double* out, std::string* err) {
+    if (C == 0) return 0;  // :161-162
+    std::ifstream in(path);
+    if (!in.is_open()) {
+        *err = "FATAL: could not open covariate file: " + path;
+        return -1;
+    }
+    std::string line;
+    std::vector<std::string> tok;
+    int64_t row = 0, lineno = 0;
+    while (std::getline(in, line)) {
+        if (++lineno == 1) continue;  // the header (:176)
+        split_ws(line, tok);
+        const int Cobs = tok.size() > 2 ? (int)(tok.size() - 2) : 0;  // after the two IDs (:183-184)
+        if (Cobs != C) {  // :191-194 (the reference exits here)
+            std::printf("FATAL: number of covariates = %d does not match to the specified number of covariates = %d\n",
+                        Cobs, C);
+            std::fflush(stdout);
+            *err = "FATAL: number of covariates = " + std::to_string(Cobs) +
+                   " does not match to the specified number of covariates = " + std::to_string(C);
+            return -2;
+        }
+        if (row < N) {
+            for (int j = 0; j < C; ++j) {
+                const char* s = tok[2 + j].c_str();
+                char* end = nullptr;
+                const double v = std::strtod(s, &end);  // std::stod (:187)
+                if (end == s) {
+                    *err = "covariate file " + path + ": \"" + tok[2 + j] + "\" is not a number";
+                    return -4;
+                }
+                out[(int64_t)j * N + row] = v;
+            }
+        }
+        ++row;
+    }
+    if (row != N) {  // (the reference would index covs[i] out of bounds, :210-225)
+        *err = "covariate rows (" + std::to_string(row) + ") != N (" + std::to_string(N) + ")";
+        return -3;
+    }
+    if (standardize) standardize_covariates(out, N, C, N);
+    return 0;
 }
 
 double standardize_phen(std::vector<double>& y) {

@@ -13,6 +13,18 @@ int64_t read_phen(const std::string& path, std::vector<double>& y);
 // (src/data.cpp:97-104).  Returns the scale factor.
 double standardize_phen(std::vector<double>& y);
 
+// data::read_covariates (src/data.cpp:159-227): a header line, then per row
+// two IDs and exactly C numeric fields, split like read_phen's.  out: C
+// columns of N (covariate-major).  0 ok; -1 cannot open; -2 a row without
+// exactly C fields (the reference's FATAL line is printed to stdout, where the
+// reference exits); -3 not N rows; -4 a field that is not a number.  *err
+// receives the message.  C == 0: nothing is read (:161-162).
+int read_covariates(const std::string& path, int64_t N, int C, bool standardize, double* out, std::string* err);
+// its standardisation (:205-226), per column (stride ld): mean and population
+// standard deviation (divided by N) accumulated in long double; a column with
+// csig < 1e-8 becomes zeros, else (v - mean)/csig
+void standardize_covariates(double* Z, int64_t N, int C, int64_t ld);
+
 // mpi_store_vec_to_file (src/utilities.cpp:241-249): CREATE|WRONLY without
 // truncation, M doubles at byte offset S*8.
 bool store_vec(const std::string& path, const double* v, int64_t S, int64_t M);

@@ -478,6 +478,34 @@ hipError_t probit_confusion(int64_t N, int nz, const double* z, int64_t ld, cons
                             hipStream_t st);
 // P2 start: p1[i] = gauss(seed ^ salt, 0, i) (replaces simulate(N, {1}, {1}), :53)
 hipError_t probit_p1(uint64_t seed, int64_t N, double* p1, hipStream_t st);
+// probit_denoise with the covariate offset: c = (p1[i] + m_cov[i]) / sqrt(1 + 1/tau1)
+// (g1_bin_class / g1d_bin_class with m_cov, :469-488); the same block sums and RedOut protocol
+hipError_t probit_denoise_cov(int64_t N, const double* p1, const double* y, const double* m_cov, double tau1,
+                              double* z1, const RedOut& ro, hipStream_t st);
+
+// ---- covariate effects of the probit model (vamp::Newton_method_cov, :490-617) --
+// Z: C covariates of N samples, covariate-major with column stride ld.  A
+// workgroup owns the tile of kCovTile samples [t*kCovTile, (t+1)*kCovTile) and
+// forms every sum over it in row order; cov_finish adds the tiles' partials in
+// tile order, one thread per sum.  No sum depends on the grid or the device,
+// and the mlogL of cov_mlogl is bitwise that of cov_eval on the same inputs.
+constexpr int kCovMaxC = 64;   // VAMPOMI_MAX_C
+constexpr int kCovTile = 64;   // samples per workgroup
+inline int64_t cov_tiles(int64_t N) { return (N + kCovTile - 1) / kCovTile; }
+inline int cov_nq(int C) { return C * (C + 1) / 2 + C + 1; }
+// Per sample: g = gg_i + sum_j Z_ij eta_j (j ascending; gg may be null: zeros),
+// s = 2 y_i - 1, arg = s g, ratio = (2/sqrt(2 pi)) / erfcx(-arg/sqrt 2),
+// lambda = ratio s, w = lambda (lambda + g)  (:536-547).  out (device, C*C + C
+// + 1 doubles): H_jk = sum Z_ij Z_ik w (j <= k formed, mirrored), rhs_j = sum
+// Z_ij lambda, mlogL = (sum -log(0.5 erfc(-arg/sqrt 2))) / N  (:490-502).
+// eta: device, C.  part: device scratch, cov_tiles(N) * cov_nq(C) doubles.
+hipError_t cov_eval(int64_t N, int C, const double* Z, int64_t ld, const double* y, const double* gg,
+                    const double* eta, double* part, double* out, hipStream_t st);
+// mlogL alone into out[0] (the line search's evaluations); part: cov_tiles(N) doubles
+hipError_t cov_mlogl(int64_t N, int C, const double* Z, int64_t ld, const double* y, const double* gg,
+                     const double* eta, double* part, double* out, hipStream_t st);
+// m[i] = sum_j Z_ij eta_j, j ascending (inner_prod(Z[i], cov_eff), :214-216)
+hipError_t cov_offset(int64_t N, int C, const double* Z, int64_t ld, const double* eta, double* m, hipStream_t st);
 
 // ---- association tests (src/main_meth.cpp:206-264, src/data.cpp:385-417) -------
 // stats[5j + {0..4}] = sum X, sum X^2, sum X*ym, sum ym, sum ym^2 over the

@@ -2674,6 +2674,182 @@ hipError_t probit_p1(uint64_t seed, int64_t N, double* p1, hipStream_t st) {
     return hipGetLastError();
 }
 
+// probit_denoise_kernel with the covariate offset m_cov (g1_bin_class /
+// g1d_bin_class with m_cov, src/vamp_probit.cpp:469-488): the same body, block
+// sums and RedOut protocol
+__global__ __launch_bounds__(kBlock) void probit_denoise_cov_kernel(int64_t N, const double* __restrict__ p1,
+                                                                    const double* __restrict__ y,
+                                                                    const double* __restrict__ m_cov, double tau1,
+                                                                    double* __restrict__ z1, RedOut ro) {
+    __shared__ double lds[4];
+    const double sq = sqrt(1.0 + 1.0 / tau1);           // sqrt(probit_var + 1/tau1)
+    const double k0 = 2.0 / sqrt(2 * M_PI), rt2 = sqrt(2.0);
+    const double den = 1 + tau1 * 1.0;                  // 1 + tau1*probit_var
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < N; i += (int64_t)gridDim.x * kBlock) {
+        const double p = p1[i], s = 2 * y[i] - 1;
+        const double c = (p + m_cov[i]) / sq;
+        const double ratio = k0 / erfcx_ref(-s * c / rt2);
+        z1[i] = p + s * ratio / tau1 / sq;
+        acc += 1 - ratio / den * (s * c + ratio);
+    }
+    acc = block_sum(acc, lds);
+    if (threadIdx.x == 0) red_put(ro, blockIdx.x, acc);
+    red_finish(ro, 1, lds);
+}
+
+hipError_t probit_denoise_cov(int64_t N, const double* p1, const double* y, const double* m_cov, double tau1,
+                              double* z1, const RedOut& ro, hipStream_t st) {
+    hipLaunchKernelGGL(probit_denoise_cov_kernel, dim3(red_blocks(N)), dim3(kBlock), 0, st, N, p1, y, m_cov, tau1, z1,
+                       ro);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// probit model: covariate effects (vamp::Newton_method_cov, mlogL_probit,
+// src/vamp_probit.cpp:490-617)
+// ---------------------------------------------------------------------------
+// entry e of the upper triangle, rows in order: (0,0) .. (0,C-1), (1,1) ..
+__device__ __forceinline__ void cov_tri(int e, int C, int& j, int& k) {
+    j = 0;
+    while (e >= C - j) {
+        e -= C - j;
+        ++j;
+    }
+    k = j + e;
+}
+
+// One tile of kCovTile samples per workgroup.  FULL (256 threads): the tile's
+// Z rows are staged in LDS (row stride C | 1: the lanes' (j, k) reads spread
+// over the banks), threads 0..nr-1 form g, lambda, w and -log Phi(arg) of their
+// row, then thread e forms sum number e over the tile's rows in row order:
+// the C(C+1)/2 upper entries of H, the C of rhs, the mlogL sum, written to
+// part[tile*nq + e].  !FULL (64 threads): the mlogL sum alone, part[tile], by
+// the same operations in the same order.
+template <bool FULL>
+__global__ __launch_bounds__(kBlock) void cov_tile_kernel(int64_t N, int C, const double* __restrict__ Z, int64_t ld,
+                                                          const double* __restrict__ y,
+                                                          const double* __restrict__ gg,
+                                                          const double* __restrict__ eta,
+                                                          double* __restrict__ part) {
+    constexpr int T = kCovTile;
+    __shared__ double zt[FULL ? T * (kCovMaxC + 1) : 1];
+    __shared__ double lam[T], w[T], ml[T], et[kCovMaxC];
+    const int CS = C | 1, tid = threadIdx.x;
+    const int64_t i0 = (int64_t)blockIdx.x * T;
+    const int nr = (int)(N - i0 < T ? N - i0 : T);
+    if (tid < C) et[tid] = eta[tid];
+    if constexpr (FULL) {
+        const int r = tid & (T - 1);
+        for (int j = tid / T; j < C; j += kBlock / T) zt[r * CS + j] = r < nr ? Z[(int64_t)j * ld + i0 + r] : 0.0;
+    }
+    __syncthreads();
+    if (tid < nr) {
+        const int64_t i = i0 + tid;
+        double s = 0.0;  // inner_prod(Z[i], eta)
+        for (int j = 0; j < C; ++j) {
+            double zij;
+            if constexpr (FULL)
+                zij = zt[tid * CS + j];
+            else
+                zij = Z[(int64_t)j * ld + i];
+            s += zij * et[j];
+        }
+        const double g = (gg ? gg[i] : 0.0) + s;
+        const double sg = 2 * y[i] - 1;
+        const double arg = sg * g;
+        if constexpr (FULL) {
+            const double ratio = 2.0 / sqrt(2 * M_PI) / erfcx_ref(-arg / sqrt(2.0));
+            const double l = ratio * sg;
+            lam[tid] = l;
+            w[tid] = l * (l + g);
+        }
+        ml[tid] = -log(0.5 * erfc(-arg * M_SQRT1_2));  // -log(normal_cdf(arg))
+    }
+    __syncthreads();
+    const int nH = C * (C + 1) / 2, nq = FULL ? nH + C + 1 : 1;
+    for (int e = tid; e < nq; e += (int)blockDim.x) {
+        double acc = 0.0;
+        if (e == nq - 1) {
+            for (int r = 0; r < nr; ++r) acc += ml[r];
+        } else if (e < nH) {
+            int j, k;
+            cov_tri(e, C, j, k);
+            for (int r = 0; r < nr; ++r) acc += zt[r * CS + j] * zt[r * CS + k] * w[r];
+        } else {
+            const int j = e - nH;
+            for (int r = 0; r < nr; ++r) acc += zt[r * CS + j] * lam[r];
+        }
+        part[(int64_t)blockIdx.x * nq + e] = acc;
+    }
+}
+
+// sum number q over the tiles in tile order, one thread per sum; full: out =
+// H (C*C, mirrored), rhs (C), mlogL/N; else out[0] = mlogL/N
+__global__ __launch_bounds__(kBlock) void cov_finish_kernel(int64_t ntiles, int nq, int C, int64_t N,
+                                                            const double* __restrict__ part, double* __restrict__ out,
+                                                            int full) {
+    const int q = (int)(blockIdx.x * kBlock + threadIdx.x);
+    if (q >= nq) return;
+    double s = 0.0;
+    for (int64_t t = 0; t < ntiles; ++t) s += part[t * nq + q];
+    if (!full) {
+        out[0] = s / (double)N;
+        return;
+    }
+    const int nH = C * (C + 1) / 2;
+    if (q == nq - 1) {
+        out[C * C + C] = s / (double)N;
+    } else if (q >= nH) {
+        out[C * C + (q - nH)] = s;
+    } else {
+        int j, k;
+        cov_tri(q, C, j, k);
+        out[j * C + k] = s;
+        out[k * C + j] = s;
+    }
+}
+
+static bool cov_args_ok(int64_t N, int C, const double* Z, int64_t ld) {
+    return N >= 1 && C >= 1 && C <= kCovMaxC && Z && ld >= N;
+}
+
+hipError_t cov_eval(int64_t N, int C, const double* Z, int64_t ld, const double* y, const double* gg,
+                    const double* eta, double* part, double* out, hipStream_t st) {
+    if (!cov_args_ok(N, C, Z, ld) || !y || !eta || !part || !out) return hipErrorInvalidValue;
+    const int64_t nt = cov_tiles(N);
+    const int nq = cov_nq(C);
+    hipLaunchKernelGGL(cov_tile_kernel<true>, dim3((unsigned)nt), dim3(kBlock), 0, st, N, C, Z, ld, y, gg, eta, part);
+    hipLaunchKernelGGL(cov_finish_kernel, dim3((unsigned)cdiv(nq, kBlock)), dim3(kBlock), 0, st, nt, nq, C, N, part,
+                       out, 1);
+    return hipGetLastError();
+}
+
+hipError_t cov_mlogl(int64_t N, int C, const double* Z, int64_t ld, const double* y, const double* gg,
+                     const double* eta, double* part, double* out, hipStream_t st) {
+    if (!cov_args_ok(N, C, Z, ld) || !y || !eta || !part || !out) return hipErrorInvalidValue;
+    const int64_t nt = cov_tiles(N);
+    hipLaunchKernelGGL(cov_tile_kernel<false>, dim3((unsigned)nt), dim3(kCovTile), 0, st, N, C, Z, ld, y, gg, eta,
+                       part);
+    hipLaunchKernelGGL(cov_finish_kernel, dim3(1), dim3(kBlock), 0, st, nt, 1, C, N, part, out, 0);
+    return hipGetLastError();
+}
+
+__global__ void cov_offset_kernel(int64_t N, int C, const double* __restrict__ Z, int64_t ld,
+                                  const double* __restrict__ eta, double* __restrict__ m) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= N) return;
+    double s = 0.0;
+    for (int j = 0; j < C; ++j) s += Z[(int64_t)j * ld + i] * eta[j];
+    m[i] = s;
+}
+
+hipError_t cov_offset(int64_t N, int C, const double* Z, int64_t ld, const double* eta, double* m, hipStream_t st) {
+    if (!cov_args_ok(N, C, Z, ld) || !eta || !m) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cov_offset_kernel, dim3((unsigned)cdiv(N, kBlock)), dim3(kBlock), 0, st, N, C, Z, ld, eta, m);
+    return hipGetLastError();
+}
+
 
 // ---------------------------------------------------------------------------
 // association tests: data::pvals_loo (src/data.cpp:385-417) and the SE

@@ -172,6 +172,21 @@ int main(int argc, char** argv) {
         return EXIT_FAILURE;
     }
 
+    // data::read_covariates (src/data.cpp:159-227), on every rank, before any
+    // device call: a malformed table ends the job here as it ends the
+    // reference's (every rank reads the same file and fails alike).  Only the
+    // probit model uses them (src/vamp_probit.cpp:62-95)
+    const bool use_cov = opt.run_mode == "infere" && opt.model == "bin_class" && opt.C > 0;
+    std::vector<double> covs;
+    if (use_cov) {
+        if (opt.C <= VAMPOMI_MAX_C) covs.assign((size_t)opt.C * (size_t)opt.N, 0.0);
+        if (vampomi_parse_covariates(opt.cov_file.c_str(), (int64_t)opt.N, (int)opt.C, 1, covs.data()) != VAMPOMI_OK)
+            return die("covariates");
+    } else if (opt.run_mode == "infere" && opt.C > 0 && rank == 0) {
+        std::cout << "INFO   : --C " << opt.C << ": covariates are used by --model bin_class only and are ignored"
+                  << std::endl;
+    }
+
     unsigned char id[VAMPOMI_UNIQUE_ID_BYTES] = {0};
     std::string rdzv_path;
     // launch time (a job without a run nonce accepts only rendezvous files
@@ -286,7 +301,29 @@ int main(int argc, char** argv) {
     // as the reference does (src/vamp.cpp:396-401, rank 0): one step is one
     // iteration, and the host waits once per iteration, at its end
     auto t1 = std::chrono::steady_clock::now();
+    if (use_cov && vampomi_set_covariates(ctx, covs.data(), (int)opt.C, (int64_t)opt.N, 0) != VAMPOMI_OK)
+        return die("covariates");
     if (vampomi_vamp_begin(ctx, &p, &r) != VAMPOMI_OK) return die("inference");
+    if (use_cov) {  // src/vamp_probit.cpp:84-91, and the effects as a file
+        std::vector<double> eff((size_t)opt.C);
+        if (vampomi_get_cov_eff(ctx, eff.data()) != VAMPOMI_OK) return die("covariate effects");
+        if (rank == 0) {
+            for (unsigned i0 = 0; i0 < opt.C; i0++) {
+                std::cout << "cov_eff[" << i0 << "] = " << eff[i0] << ", ";
+                if (i0 % 4 == 3) std::cout << std::endl;
+            }
+            std::cout << std::endl;
+            if (!opt.out_dir.empty()) {
+                const std::string path = opt.out_dir + "/" + opt.out_name + "_cov_eff.bin";
+                ::unlink(path.c_str());
+                if (!vio::store_vec(path, eff.data(), 0, (int64_t)opt.C)) {
+                    std::cout << "FATAL  : cannot write " << path << std::endl;
+                    vampomi_comm_abort(ctx);
+                    return EXIT_FAILURE;
+                }
+            }
+        }
+    }
     double total = 0.0;
     for (int stopped = 0; !stopped;) {
         const auto ts0 = std::chrono::steady_clock::now();

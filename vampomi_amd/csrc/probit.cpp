@@ -43,6 +43,17 @@ vampomi_status probit_begin(vampomi_ctx* c, VampRun& R) {
     HIPCHK(hipMemsetAsync(R.r1, 0, M * 8, c->st));         // r1 = r2 = 0 (:56-57)
     R.tau1 = R.gam1;                                       // :35
     R.alpha1 = 0;                                          // :58
+    // cov_eff = Newton_method_cov(y, gg = z1_hat = 0, Z, 0) before iteration 1
+    // (:60-63, :78-82), and the offsets m_cov_i = Z_i.cov_eff every z-side
+    // denoising then uses (:213-233): neither changes during the run
+    c->cov_eff.assign((size_t)c->cov_C, 0.0);
+    if (c->cov_C > 0) {
+        STCHK(cov_newton_dev(c, nullptr, nullptr, c->cov_eff.data(), nullptr, nullptr, nullptr));
+        STCHK(dev_alloc(&R.m_cov, ld));
+        HIPCHK(hipMemsetAsync(R.m_cov, 0, ld * 8, c->st));
+        STCHK(cov_offset_dev(c, c->cov_eff.data(), R.m_cov));
+    }
+    c->cov_fitted = true;
     if (R.write) {
         R.p_metrics = R.out_dir + "/" + R.out_name + "_metrics.csv";
         R.p_params = R.out_dir + "/" + R.out_name + "_params.csv";
@@ -111,7 +122,10 @@ vampomi_status probit_step(vampomi_ctx* c, VampRun& R) {
     auto queue_z = [&](DotBatch& b, const double* x1v, const double* zx, double* bs, double* cnt, double* xc) {
         vk::RedOut ro{};
         STCHK(b.sink(1, false, bs, &ro));  // y, p1 replicated: local sum
-        HIPCHK(vk::probit_denoise(N, R.p1, c->y, R.tau1, R.z1h, ro, c->st));
+        if (R.m_cov)
+            HIPCHK(vk::probit_denoise_cov(N, R.p1, c->y, R.m_cov, R.tau1, R.z1h, ro, c->st));
+        else
+            HIPCHK(vk::probit_denoise(N, R.p1, c->y, R.tau1, R.z1h, ro, c->st));
         STCHK(b.sink(4, false, cnt, &ro));
         HIPCHK(vk::probit_confusion(N, 1, zx, ld, c->y, ro, c->st));
         STCHK(b.add({T(x1v, R.ts), T(x1v, x1v), T(R.ts, R.ts)}, M, true, xc));
@@ -306,5 +320,18 @@ vampomi_status probit_step(vampomi_ctx* c, VampRun& R) {
         res->a_passes_ref = R.passes_ref;
         res->a_passes_exec = c->stats.a_passes_exec;
     }
+    return VAMPOMI_OK;
+}
+
+extern "C" vampomi_status vampomi_get_probit_state(vampomi_ctx* c, double* p1, double* tau1) {
+    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
+    if (!c->run || !c->run->probit) return fail(VAMPOMI_ERR_STATE, "no bin_class run in progress");
+    VampRun& R = *c->run;
+    HIPCHK(hipSetDevice(c->device));
+    if (p1) {
+        HIPCHK(hipMemcpyAsync(p1, R.p1, (size_t)c->N * 8, hipMemcpyDeviceToHost, c->st));
+        STCHK(sync_stream(c, c->st));
+    }
+    if (tau1) *tau1 = R.tau1;
     return VAMPOMI_OK;
 }

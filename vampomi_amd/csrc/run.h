@@ -93,6 +93,7 @@ struct VampRun {
     double* x1s = nullptr;  // M: x1_hat / sqrt(N)
     double* x1sn = nullptr; // M: next iteration's x1_hat / sqrt(N)
     double* x2s = nullptr;  // M: x2_hat / sqrt(N)
+    double* m_cov = nullptr;  // N: Z.cov_eff, the z-denoiser's offset (null: a run without covariates)
     double* prior_row = nullptr;  // host staging, unused by the linear model
     // the last step's phases as the host sees them (vampomi_step_phases): the
     // solves (entering pcg_run to its return: the device's CG and Onsager

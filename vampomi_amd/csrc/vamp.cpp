@@ -49,7 +49,7 @@
 VampRun::~VampRun() {
     if (writer) writer->drain(nullptr);  // its kernels read x1 / r1, its thread writes the caller's history arrays
     for (double** p : {&r1, &x1, &x1p, &x1n, &x1d, &r2, &x2, &bern, &invQ, &v, &atxy, &ts, &tmpM, &atx0, &z1buf,
-                       &nb3, &nsc, &ax2, &p1, &p2, &z1h, &x1s, &x1sn, &x2s, &abern, &bern_next, &pre_t1, &pre_u1})
+                       &nb3, &nsc, &ax2, &p1, &p2, &z1h, &x1s, &x1sn, &x2s, &abern, &bern_next, &pre_t1, &pre_u1, &m_cov})
         dev_free(*p);
     for (auto& p : cgw) dev_free(p);
     dev_free(mixw);
@@ -290,6 +290,7 @@ extern "C" vampomi_status vampomi_vamp_begin(vampomi_ctx* c, const vampomi_param
     HIPCHK(hipSetDevice(c->device));
     STCHK(op_agree(c));  // several ranks: the one-pass / head-start choice, agreed here, where every rank is
     c->run.reset(new VampRun());
+    c->cov_fitted = false;  // (vampomi_get_cov_eff: the effects of THIS run, fitted by probit_begin)
     c->pre_made_n = c->pre_used_n = 0;  // (a new run: no pre-step products carried over, VampRun.pre_it = 0)
     VampRun& R = *c->run;
     R.prm = *p;
