@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 from conftest import relerr
+import _mix
 from _data import make_problem
 
 pytestmark = pytest.mark.gpu
@@ -177,6 +178,64 @@ def test_se_parity():
         d.load_meth(X)
         p = d.assoc_se(r1, gam1)
     assert np.allclose(p, po, rtol=1e-14, atol=1e-16)
+
+
+@pytest.mark.parametrize("N", _mix.PVAL_NS)
+def test_small_sample_pvalue_function(N):
+    """t_sf / lnbeta_half on the device (OCML's lgamma, log1p, log, exp) at
+    df = N - 2 = 1, 2, 3, 7, 30, 59, 60, 61, 62 (the lgamma branch, both sides
+    of its a = 30 series boundary, odd and even N) with one designed marker per
+    |t| in 0 ... 1e3, both sides of the t >= 3 branch switch included
+    (_mix.pval_problem); est = 0: the plain marginal regression on y.
+
+    Bars: the five sums to 1e-12 of the sum of their terms' magnitudes (numpy);
+    p against the oracle's p-value function of the device's own sums to 1e-12
+    (_check_pfun).  A value that misses that still passes if it is no further
+    from mpmath's incomplete beta function of the same sums than twice the
+    oracle's distance (the oracle itself is within 1e-9 of it:
+    tests/test_mixture_refs.py); such values are recorded."""
+    X, y = _mix.pval_problem(N)
+    with va.Data(N, _mix.PVAL_MT) as d:
+        d.load_meth(X)
+        d.set_phen(y, standardize=False)
+        p, st = d.assoc_loo(np.zeros(_mix.PVAL_MT))
+    terms = [X, X * X, X * y[None, :], np.broadcast_to(y, X.shape), np.broadcast_to(y * y, X.shape)]
+    for q, tq in enumerate(terms):
+        assert np.all(np.abs(st[:, q] - tq.sum(1)) <= 1e-12 * np.abs(tq).sum(1)), q
+    assert np.all(np.isfinite(p)) and np.all((p >= 0) & (p <= 1))
+    pf = np.array([O.reg1d_pval(*s, N) for s in st])
+    miss = np.nonzero(~(np.abs(p - pf) <= 1e-12 * pf + 1e-300))[0]
+    for j in miss:
+        pm = _mix.pval_mp(st[j], N)
+        print(f"N={N} marker {j}: p gpu {p[j]:.17e} oracle {pf[j]:.17e} mpmath {pm:.17e}")
+        _mix.record("pval", N=N, marker=int(j), gpu=float(p[j]), oracle=float(pf[j]), mpmath=pm)
+        assert abs(p[j] - pm) <= 2 * abs(pf[j] - pm), (N, j, p[j], pf[j], pm)
+    nt = len(_mix.PVAL_TS)
+    assert p[0] > 0.99 and np.all(np.diff(p[:nt]) < 0)  # the designed |t| increase
+
+
+def test_se_tails():
+    """se_pval_kernel out to |r1| = 36 sd (p ~ 1e-284), +-0 and +-1e-300:
+    the oracle's values at test_se_parity's tolerances, its exact zeros and
+    halves where 1 - p rounds (r1 <= 0), and in the upper tail relative 1e-14,
+    or, where the device's erfc misses that, 4x the oracle's own relative
+    error against mpmath's erfc of the same double argument (recorded)."""
+    r1 = _mix.se_r1()
+    po = O.assoc_se(r1, _mix.SE_GAM1, _mix.SE_N)
+    with va.Data(_mix.SE_N, len(r1)) as d:
+        p = d.assoc_se(r1, _mix.SE_GAM1)
+    assert np.allclose(p, po, rtol=1e-14, atol=1e-16)
+    exact = (po == 0.0) | (po == 1.0) | (po == 0.5)
+    assert exact.sum() > 60 and np.array_equal(p[exact], po[exact])
+    pos = np.nonzero(r1 > 1e-300)[0]
+    miss = pos[~(np.abs(p[pos] - po[pos]) <= 1e-14 * po[pos])]
+    if len(miss):
+        pm = _mix.se_mp(r1[miss])
+        eg, eo = np.abs(p[miss] - pm) / pm, np.abs(po[miss] - pm) / pm
+        for j, a, b in zip(miss, eg, eo):
+            print(f"r1/sd = {r1[j] * math.sqrt(_mix.SE_GAM1 * _mix.SE_N):.2f}: rel. error gpu {a:.3e} oracle {b:.3e}")
+            _mix.record("se", z=float(r1[j] * math.sqrt(_mix.SE_GAM1 * _mix.SE_N)), gpu=float(a), oracle=float(b))
+        assert np.all(eg <= 4 * eo), (eg.max(), eo.max())
 
 
 def test_cli_association_files(tmp_path):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import relerr
+import _mix
 from _data import make_problem
 
 pytestmark = pytest.mark.gpu
@@ -101,6 +102,25 @@ def test_update_prior_entry_point(em, lv, merge):
         p, v = d.update_prior(r1, 35.0, O.DEFAULT_PROBS, vars_s, EM_max_iter=em, learn_vars=lv, merge_vars_thr=merge)
     assert len(p) == len(po)
     assert np.allclose(p, po, rtol=1e-12, atol=0) and np.allclose(v, vo, rtol=1e-12, atol=0)
+
+
+@pytest.mark.parametrize("M", _mix.PRIOR_MS)
+def test_update_prior_large_mixtures(M):
+    """updatePrior alone at mix(L), L on both sides of em_kernel's 11 register
+    slabs (kEmC = 12) up to 64, at M around a wave, a block and red_blocks'
+    512, and at M = 524289, where em_kernel launches more than 2048 blocks of
+    Q = 1 + 2(L-1) partials each: the oracle's L, probs and vars to 1e-12.
+    (tests/test_mixture_refs.py: the oracle's own result does not depend on
+    the order of r1 beyond 1e-13 for these inputs, so no merge is borderline.)"""
+    r1 = _mix.prior_r1(M)
+    with va.Data(_mix.N_SMALL, M) as d:
+        d.generate(12, va.GEN_GAUSS)
+        for L, em, lv, mg in _mix.prior_cases(M):
+            probs, vars_s = _mix.mix(L, _mix.N_SMALL)
+            po, vo = _mix.oracle_prior(r1, L, em, lv, mg)
+            p, v = d.update_prior(r1, _mix.PRIOR_GAM1, probs, vars_s, EM_max_iter=em, learn_vars=lv, merge_vars_thr=mg)
+            assert len(p) == len(po), (L, em, lv, mg)
+            assert np.allclose(p, po, rtol=1e-12, atol=0) and np.allclose(v, vo, rtol=1e-12, atol=0), (L, em, lv, mg)
 
 
 def test_device_memory_plan_matches_the_allocations(tmp_path):

@@ -10,6 +10,7 @@ from conftest import relerr
 import os
 
 from _data import PROBIT_K, make_problem, oracle_with_spread, record_probit_ratio
+from _mix import mix_kw
 
 pytestmark = pytest.mark.gpu
 
@@ -30,6 +31,14 @@ CASES = {
     "gam1_h2": dict(gam1=1e-3, h2=0.3),
     "cg_loose": dict(CG_err_tol=1e-3, CG_max_iter=4),
     "cg_tight": dict(CG_err_tol=1e-9),
+    # mixtures beyond em_kernel's register slabs (kEmC = 12: slabs j >= 12 take
+    # its run-time loops) up to the ABI's 64 components; with EM_max_iter = 1
+    # the device's own update and merge (em_update_mix) carries them
+    "mix13": mix_kw(13),
+    "mix16_merge": mix_kw(16),  # L crosses 12 in mid-run
+    "mix64_merge": mix_kw(64),
+    "mix24_nomerge": mix_kw(24, merge_vars_thr=0.0),
+    "mix64_em3": mix_kw(64, merge_vars_thr=0.0, EM_max_iter=3),  # the host EM path, Q = 127 sums
 }
 
 
@@ -68,15 +77,30 @@ def test_linear_options(case):
     X, y, beta = make_problem(N, MT, seed=5)
     kw = dict(max_iter=12, stop_criteria_thr=0.0, **CASES[case])
     ref = O.vamp_infere(X, y, MT, true_signal=beta, **kw)
+    _check_case_keeps_its_point(case, ref)
     _check(_gpu(X, y, beta, "linear", **kw), ref)
 
 
-@pytest.mark.parametrize("case", ["three_slabs", "em3_tight", "fixed_vars", "no_damping", "cg_loose"])
+def _check_case_keeps_its_point(case, ref):
+    """The large-mixture cases name an L history; the reference must show it."""
+    if not case.startswith("mix"):
+        return
+    L = ref["L"]
+    assert L.max() > 12, L
+    if case == "mix16_merge":
+        assert L.min() <= 12, L
+    if CASES[case].get("merge_vars_thr") == 0.0:
+        assert L.min() == len(CASES[case]["vars"]), L
+
+
+@pytest.mark.parametrize("case", ["three_slabs", "em3_tight", "fixed_vars", "no_damping", "cg_loose", "mix16_merge",
+                                  "mix64_em3"])
 def test_probit_options(case):
     X, y, beta = make_problem(N, MT, seed=5)
     yb = (y > 0).astype(np.float64)
     kw = dict(max_iter=10, stop_criteria_thr=0.0, model="bin_class", **CASES[case])
     ref, spread = oracle_with_spread(X, yb, beta, MT, ranks=(2, 3), **kw)
+    _check_case_keeps_its_point(case, ref)
     _check(_gpu(X, yb, beta, **kw), ref, spread)
 
 

@@ -17,6 +17,7 @@ import pytest
 
 from conftest import relerr
 from _data import PROBIT_K, make_problem, oracle_with_spread, record_probit_ratio
+from _mix import mix_kw
 
 pytestmark = pytest.mark.gpu
 
@@ -124,6 +125,45 @@ def test_sharded_linear_vamp_matches_single_rank(monkeypatch, P):
     ref = O.vamp_infere(X, y, Mt, true_signal=beta, **kw)
     assert relerr(_cat(parts, "x1_final"), ref["x1_final"]) < 1e-10
     assert parts[0]["cg_iters"] == ref["cg_iters"].tolist()
+
+
+_LARGE_MIX = {"mix16_merge": mix_kw(16), "mix64_nomerge": mix_kw(64, merge_vars_thr=0.0)}
+_large_mix_refs = {}  # case -> (problem, one-rank GPU run, oracle run): made once, shared by the P's
+
+
+@pytest.mark.parametrize("P", [2, 3])
+@pytest.mark.parametrize("case", sorted(_LARGE_MIX))
+def test_sharded_large_mixture_matches_single_rank(monkeypatch, case, P):
+    """Mixtures beyond em_kernel's 11 register slabs on several ranks: the EM
+    round's update and merge run in tail_post_kernel (mode 1) after the
+    all-reduce of the 1 + 2(L-1) sums.  mix(16) merges across 12 components in
+    mid-run, mix(64) without merging stays at the ABI's widest."""
+    N, Mt, its = 600, 1100, 8
+    kw = dict(max_iter=its, stop_criteria_thr=0.0, **_LARGE_MIX[case])
+    if case not in _large_mix_refs:
+        X, y, beta = make_problem(N, Mt)
+        with va.Data(N, Mt) as d:
+            one = _vamp(d, X, y, beta, **kw)
+        _large_mix_refs[case] = (X, y, beta), one, O.vamp_infere(X, y, Mt, true_signal=beta, **kw)
+    (X, y, beta), one, ref = _large_mix_refs[case]
+    if case == "mix16_merge":
+        assert ref["L"].max() > 12 and ref["L"].min() <= 12, ref["L"]
+    else:
+        assert ref["L"].min() == 64, ref["L"]
+    parts = run_ranks(monkeypatch, P, N, Mt, lambda r, d: _vamp(d, X, y, beta, **kw))
+    for p in parts:
+        assert p["cg_iters"] == one["cg_iters"] and p["ons_iters"] == one["ons_iters"] and p["L"] == one["L"]
+        assert np.allclose(p["params"], one["params"], rtol=1e-11)
+        assert np.allclose(p["metrics"], one["metrics"], rtol=1e-11, equal_nan=True)
+    for k in range(its):
+        assert relerr(_cat(parts, "x1_hist")[k], one["x1_hist"][k]) < 1e-12, k
+        assert relerr(_cat(parts, "r1_hist")[k], one["r1_hist"][k]) < 1e-12, k
+    assert parts[0]["cg_iters"] == ref["cg_iters"].tolist() and parts[0]["ons_iters"] == ref["ons_iters"].tolist()
+    assert parts[0]["L"] == ref["L"].tolist()
+    assert relerr(_cat(parts, "x1_final"), ref["x1_final"]) < 1e-10
+    for k in range(its):
+        assert relerr(_cat(parts, "x1_hist")[k], ref["x1_hist"][k]) <= 1e-10, k
+        assert relerr(_cat(parts, "r1_hist")[k], ref["r1_hist"][k]) <= 1e-10, k
 
 
 @pytest.mark.parametrize("P", [2, 4, 8])
