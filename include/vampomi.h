@@ -66,7 +66,8 @@ typedef enum {
     VAMPOMI_ERR_NAN_PHEN = 5,     /* "NA" in phenotype file (src/data.cpp:73-74) */
     VAMPOMI_ERR_STATE = 6,        /* call out of order (e.g. Ax before data load) */
     VAMPOMI_ERR_OOM = 7,          /* device or host allocation failed */
-    VAMPOMI_ERR_MODEL = 8         /* unsupported --model (src/vamp.cpp:103-104) */
+    VAMPOMI_ERR_MODEL = 8,        /* unsupported --model (src/vamp.cpp:103-104) */
+    VAMPOMI_ERR_RANGE = 9         /* methylation values a VAMPOMI_STORE_U16 shard cannot hold */
 } vampomi_status;
 
 /* where a caller buffer lives */
@@ -85,6 +86,19 @@ typedef enum {
  * computes on the widened copy of the same stored values. */
 #define VAMPOMI_STORE_F64 0       /* doubles (the default; the reference's file format) */
 #define VAMPOMI_STORE_F32 1       /* floats: fp64 input is rounded to nearest even at ingest */
+/* 16-bit fixed point: the stored element is a uint16 k meaning k * 2^-16, a
+ * quarter of the doubles' memory and bytes per pass.  Methylation beta values
+ * lie in [0, 1]; the grid's absolute error is at most 2^-17 (7.7e-6) everywhere
+ * in [0, 1 - 2^-17), below the data's last digit.  An input x (fp64 or fp32) is
+ * stored as k = min(65535, rint(x * 65536)), ties to even: 0 <= x <= 1 is
+ * accepted (-0.0 is 0; x >= 1 - 2^-17, 1.0 included, is CLAMPED to 65535);
+ * NaN, +-inf, x < 0 and x > 1 are REJECTED: the load returns VAMPOMI_ERR_RANGE,
+ * vampomi_last_error gives the number of rejected entries and the smallest
+ * offending (marker, row) (the global marker index), and the context is left
+ * without a shard, as after an I/O error.  The widening (double)k * 2^-16 is
+ * exact, so a U16 context computes, bit for bit, what an F64 context computes
+ * on the dequantised matrix.  (16, not 2: the value is the element's bits.) */
+#define VAMPOMI_STORE_U16 16
 
 typedef struct vampomi_ctx vampomi_ctx;
 
@@ -128,32 +142,50 @@ vampomi_status vampomi_all_ok(vampomi_ctx* ctx, int local_ok, int* all_ok);
 vampomi_status vampomi_comm_abort(vampomi_ctx* ctx);
 
 /* ---- data ingest (data::data) ---- */
-/* The storage of the shard, VAMPOMI_STORE_F64 (the default) or _F32.  Legal
+/* The storage of the shard, VAMPOMI_STORE_F64 (the default), _F32 or _U16.  Legal
  * only before the shard is allocated, i.e. before any vampomi_load_meth_* or
  * vampomi_generate_meth: VAMPOMI_ERR_STATE afterwards, VAMPOMI_ERR_ARG for
- * any other value.  VAMPOMI_STORAGE=f32|f64 in the environment sets the default
+ * any other value.  VAMPOMI_STORAGE=f64|f32|u16 in the environment sets the default
  * at vampomi_open (any other value: vampomi_open fails with VAMPOMI_ERR_ARG).
  * Rank-local: the ranks of a job need not agree on it.  The column stride ld
- * (elements) and every kernel plan are the same for both storages. */
+ * (elements) and every kernel plan are the same for all storages. */
 vampomi_status vampomi_set_storage(vampomi_ctx* ctx, int storage);
 vampomi_status vampomi_get_storage(const vampomi_ctx* ctx, int* storage);
 /* marker-major fp64 file (README.md:15): this shard's bytes [S*N*8, (S+M)*N*8).
- * On an F32 context each chunk is staged on the device as fp64 and rounded
- * there (nearest even) into the column layout. */
+ * On an F32 or U16 context each chunk is staged on the device as fp64 and
+ * rounded (nearest even) or quantised (VAMPOMI_STORE_U16: range-checked,
+ * VAMPOMI_ERR_RANGE) there into the column layout. */
 vampomi_status vampomi_load_meth_file(vampomi_ctx* ctx, const char* path);
 /* the same marker-major layout with 4-byte float elements: this shard's bytes
  * [S*N*4, (S+M)*N*4), through the same read pipeline; widened (exactly) on an
- * F64 context */
+ * F64 context, quantised on a U16 one */
 vampomi_status vampomi_load_meth_file_f32(vampomi_ctx* ctx, const char* path);
+/* the same layout with 2-byte little-endian uint16 elements k meaning k * 2^-16
+ * (VAMPOMI_STORE_U16's own format): this shard's bytes [S*N*2, (S+M)*N*2).
+ * Loads into any storage: copied as it is on a U16 context, widened exactly on
+ * an F32 or F64 one (k * 2^-16 is exactly a float too) */
+vampomi_status vampomi_load_meth_file_u16(vampomi_ctx* ctx, const char* path);
 /* host shard: M columns of N samples, column stride ld_in >= N doubles
- * (rounded on the device on an F32 context) */
+ * (rounded on the device on an F32 context, quantised there on a U16 one) */
 vampomi_status vampomi_load_meth_host(vampomi_ctx* ctx, const double* X, int64_t ld_in);
-/* host shard of floats, column stride ld_in >= N floats, for either storage
- * (widened exactly on an F64 context) */
+/* host shard of floats, column stride ld_in >= N floats, for any storage
+ * (widened exactly on an F64 context, quantised on a U16 one) */
 vampomi_status vampomi_load_meth_host_f32(vampomi_ctx* ctx, const float* X, int64_t ld_in);
+/* host shard of uint16 k meaning k * 2^-16, column stride ld_in >= N elements,
+ * for any storage (widened exactly on an F32 or F64 context) */
+vampomi_status vampomi_load_meth_host_u16(vampomi_ctx* ctx, const uint16_t* X, int64_t ld_in);
+/* What the last load or generation of a U16 context did to its input: *clamped
+ * = the accepted entries that rounded to 65536 and were stored as 65535,
+ * *max_abs_err = the maximum over the shard of |stored value - input| (fp64; a
+ * count and a maximum, so neither depends on the order of the device's work).
+ * Both are zero on F64 and F32 contexts and after a uint16 input.  Either
+ * pointer may be NULL.  VAMPOMI_ERR_STATE before a shard is loaded. */
+vampomi_status vampomi_get_quant_stats(const vampomi_ctx* ctx, int64_t* clamped, double* max_abs_err);
 /* synthetic shard generated on the device (bit-identical to the oracle's; an
  * F32 context stores the generator's value rounded: VAMPOMI_GEN_GAUSS values
- * are exactly floats, VAMPOMI_GEN_METH values are not) */
+ * are exactly floats, VAMPOMI_GEN_METH values are not; a U16 context stores
+ * VAMPOMI_GEN_METH values quantised and refuses VAMPOMI_GEN_GAUSS with
+ * VAMPOMI_ERR_RANGE before generating anything) */
 vampomi_status vampomi_generate_meth(vampomi_ctx* ctx, uint64_t seed, int kind);
 /* PLINK phenotype, standardize = scale to unit variance, NOT centred */
 vampomi_status vampomi_read_phen(vampomi_ctx* ctx, const char* path, int standardize);
@@ -221,11 +253,11 @@ vampomi_status vampomi_newton_cov(vampomi_ctx* ctx, const double* gg, const doub
  * bin_class run on this context (C doubles; nothing when it holds no
  * covariates); VAMPOMI_ERR_STATE before that */
 vampomi_status vampomi_get_cov_eff(vampomi_ctx* ctx, double* out);
-/* (the statistics of the STORED values, accumulated in fp64) */
+/* (the statistics of the STORED values, rounded or quantised, accumulated in fp64) */
 vampomi_status vampomi_get_marker_stats(vampomi_ctx* ctx, double* mave, double* msig);
 /* copy local markers [i0, i0+count) back to the host, count x N doubles
- * (data::get_meth_data, src/data.hpp:53); an F32 context returns the stored
- * values widened, each exactly a float */
+ * (data::get_meth_data, src/data.hpp:53); an F32 or U16 context returns the
+ * stored values widened (exactly): each a float, or a multiple of 2^-16 */
 vampomi_status vampomi_read_markers(vampomi_ctx* ctx, int64_t i0, int64_t count, double* out);
 
 /* ---- operators ---- */
@@ -444,7 +476,8 @@ vampomi_status vampomi_dev_prestep_counts(const vampomi_ctx* ctx, int64_t* made,
 vampomi_status vampomi_dev_time_pass(vampomi_ctx* ctx, int which, int K, int reps, double* avg_ms);
 /* The HBM read ceiling of this device for this shard: a pure read stream of
  * the resident matrix (every byte once, 16-byte nontemporal loads, 8-byte ones
- * of an F32 context's floats: *bytes is what is resident; variant 0
+ * of an F32 context's floats, 16-byte ones again over a U16 context's bytes (a
+ * pure read is tied to no summation order): *bytes is what is resident; variant 0
  * lockstep 8-wave workgroups, one per CU, variant 1 a 1 MiB contiguous chunk
  * per wave), `reps` timed launches of each; the faster variant's median launch
  * time in *us_med, the bytes it read in *bytes, the variant in *variant.  No
@@ -454,8 +487,8 @@ vampomi_status vampomi_dev_read_ceiling(vampomi_ctx* ctx, int reps, double* us_m
  * (mode 1: the CG form, i.e. A^T.u with the lmmse_mult epilogue, A.x with the
  * fused direction update; which = 2: the association-test pass of
  * vampomi_assoc_loo) */
-/* (an F32 context launches the fp32 entry points: the same names with an _f32
- * suffix before the template arguments) */
+/* (an F32 / U16 context launches the narrow entry points: the same names with
+ * an _f32 / _u16 suffix before the template arguments) */
 vampomi_status vampomi_dev_kernel_name(const vampomi_ctx* ctx, int which, int K, int mode, char* out, int cap);
 /* The A.x plan for N samples, M markers and `cus` compute units under
  * `variant` (-1 the default, 0-6 the tile plans, 7 the team plan), no device
@@ -496,7 +529,7 @@ vampomi_status vampomi_dev_mem_plan(int64_t N, int64_t Mt, int nranks, int rank,
                                     int64_t* bytes);
 /* vampomi_dev_mem_plan with the storage named (the entry point above means
  * VAMPOMI_STORE_F64): VAMPOMI_STORE_F32 is smaller by the shard's M*ld*4
- * bytes.  VAMPOMI_ERR_ARG for any other storage. */
+ * bytes, VAMPOMI_STORE_U16 by M*ld*6.  VAMPOMI_ERR_ARG for any other storage. */
 vampomi_status vampomi_dev_mem_plan_storage(int64_t N, int64_t Mt, int nranks, int rank, int cus, int probit,
                                             int writer, int storage, int64_t* bytes);
 /* One application of the one-pass CG operator (K <= 2 systems, one rank),

@@ -21,12 +21,12 @@ from typing import Optional, Sequence
 import numpy as np
 
 from ._lib import (CLI_PATH, GEN_GAUSS, GEN_METH, LIB_PATH, MAX_L, MEM_DEVICE, MEM_HOST, STORE_F32, STORE_F64,
-                   UNIQUE_ID_BYTES, Params, Result, ShardDesc, Stats, VampomiError, check, load)
+                   STORE_U16, UNIQUE_ID_BYTES, Params, Result, ShardDesc, Stats, VampomiError, check, load)
 
 __all__ = ["Data", "Vamp", "VampOptions", "divide_work", "comm_unique_id", "VampomiError", "LIB_PATH", "CLI_PATH",
-           "GEN_GAUSS", "GEN_METH", "STORE_F64", "STORE_F32", "load"]
+           "GEN_GAUSS", "GEN_METH", "STORE_F64", "STORE_F32", "STORE_U16", "load"]
 
-_STORAGE = {"f64": STORE_F64, "f32": STORE_F32}
+_STORAGE = {"f64": STORE_F64, "f32": STORE_F32, "u16": STORE_U16}
 
 
 def _dp(a: np.ndarray):
@@ -57,17 +57,22 @@ class Data:
     :meth:`set_phen`.  Marker statistics are computed at load
     (compute_markers_statistics, src/data.cpp:233-283).
 
-    ``storage``: how the shard is held on the device, ``"f64"`` or ``"f32"``
-    (None: the library's default, ``"f64"`` unless ``VAMPOMI_STORAGE`` says
-    otherwise).  With ``"f32"`` the matrix takes half the memory and every pass
-    reads half the bytes; fp64 input is rounded to nearest even at ingest and
-    all arithmetic stays fp64.  The ``storage`` attribute tells which is in use.
+    ``storage``: how the shard is held on the device, ``"f64"``, ``"f32"`` or
+    ``"u16"`` (None: the library's default, ``"f64"`` unless ``VAMPOMI_STORAGE``
+    says otherwise).  With ``"f32"`` the matrix takes half the memory and every
+    pass reads half the bytes; fp64 input is rounded to nearest even at ingest.
+    With ``"u16"`` it takes a quarter: a value in [0, 1] is stored as the
+    ``uint16`` ``k = min(65535, rint(x * 65536))`` meaning ``k / 65536`` (at most
+    7.7e-6 off); NaN, infinities and values outside [0, 1] fail the load with
+    ``VampomiError`` (status 9, ``ERR_RANGE``; the message names the first such
+    entry), and :meth:`quant_stats` tells what the quantisation did.  All
+    arithmetic stays fp64.  The ``storage`` attribute tells which is in use.
     """
 
     def __init__(self, N: int, Mt: int, rank: int = 0, nranks: int = 1, comm_id: Optional[bytes] = None,
                  device: int = -1, alpha_scale: float = 1.0, storage: Optional[str] = None):
         if storage is not None and storage not in _STORAGE:
-            raise ValueError(f'storage must be "f64" or "f32", not {storage!r}')
+            raise ValueError(f'storage must be "f64", "f32" or "u16", not {storage!r}')
         self._lib = load()
         self._idbuf = None
         d = ShardDesc(N=N, Mt=Mt, rank=rank, nranks=nranks, device=device, comm_id=None, alpha_scale=alpha_scale)
@@ -91,7 +96,16 @@ class Data:
     def storage(self) -> str:
         s = C.c_int()
         check(self._lib.vampomi_get_storage(self.ctx, C.byref(s)))
-        return "f32" if s.value == STORE_F32 else "f64"
+        return {STORE_F32: "f32", STORE_U16: "u16"}.get(s.value, "f64")
+
+    def quant_stats(self) -> dict:
+        """What the last load of a ``"u16"`` shard did to its input: ``clamped``,
+        the entries in [1 - 2**-17, 1] stored as 65535/65536, and
+        ``max_abs_err``, the largest |stored - input|.  Zeros for the other
+        storages."""
+        n, e = C.c_int64(), C.c_double()
+        check(self._lib.vampomi_get_quant_stats(self.ctx, C.byref(n), C.byref(e)))
+        return {"clamped": n.value, "max_abs_err": e.value}
 
     # -- lifecycle --
     def close(self):
@@ -119,18 +133,25 @@ class Data:
 
     # -- ingest --
     def read_methylation_data(self, path: str, dtype: str = "f64"):
-        """The marker-major file's elements are doubles (``"f64"``) or floats (``"f32"``)."""
+        """The marker-major file's elements are doubles (``"f64"``), floats
+        (``"f32"``) or little-endian ``uint16`` k meaning k / 65536 (``"u16"``);
+        any of them loads into any storage."""
         if dtype not in _STORAGE:
-            raise ValueError(f'dtype must be "f64" or "f32", not {dtype!r}')
-        load_file = self._lib.vampomi_load_meth_file_f32 if dtype == "f32" else self._lib.vampomi_load_meth_file
+            raise ValueError(f'dtype must be "f64", "f32" or "u16", not {dtype!r}')
+        load_file = {"f64": self._lib.vampomi_load_meth_file, "f32": self._lib.vampomi_load_meth_file_f32,
+                     "u16": self._lib.vampomi_load_meth_file_u16}[dtype]
         check(load_file(self.ctx, path.encode()))
 
     def load_meth(self, X: np.ndarray):
-        """X: (M, N), this shard's markers (marker-major): float64, or float32
-        (passed as it is, with no upcast copy, for either storage)."""
+        """X: (M, N), this shard's markers (marker-major): float64, float32
+        (passed as it is, with no upcast copy) or uint16 (k meaning k / 65536),
+        for any storage."""
         if getattr(X, "dtype", None) == np.float32:
             X = np.ascontiguousarray(X)
             load_host = self._lib.vampomi_load_meth_host_f32
+        elif getattr(X, "dtype", None) == np.uint16:
+            X = np.ascontiguousarray(X)
+            load_host = self._lib.vampomi_load_meth_host_u16
         else:
             X = np.ascontiguousarray(X, dtype=np.float64)
             load_host = self._lib.vampomi_load_meth_host

@@ -37,6 +37,7 @@
 #include <cstdio>
 #include <mutex>
 #include <string>
+#include <type_traits>
 
 #include "kdev.h"
 
@@ -220,14 +221,28 @@ __device__ __forceinline__ void tm_publish_l2(unsigned long long* p, const v4u& 
 }
 
 // A row pair of a column tile through its buffer descriptor (nontemporal), as
-// loaded: 16 bytes of a double tile, 8 bytes of a float tile.  A pair past
-// the descriptor's range reads as zero either way
+// loaded: 16 bytes of a double tile, 8 bytes of a float tile, 4 bytes of a
+// 16-bit fixed-point tile.  A pair past the descriptor's range reads as zero
+// in every case (k = 0 is the value 0)
 template <class XE>
 __device__ __forceinline__ xpair_t<XE> tm_ld2(__amdgpu_buffer_rsrc_t rs, int off) {
     if constexpr (sizeof(XE) == 8)
         return __builtin_bit_cast(v2d, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 2));
-    else
+    else if constexpr (sizeof(XE) == 4)
         return __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 2));
+    else
+        return __builtin_bit_cast(v2h, __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 2));
+}
+
+// one row (the E = 1 configurations)
+template <class XE>
+__device__ __forceinline__ XE tm_ld1(__amdgpu_buffer_rsrc_t rs, int off) {
+    if constexpr (sizeof(XE) == 8)
+        return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 2));
+    else if constexpr (sizeof(XE) == 4)
+        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 2));
+    else
+        return (uint16_t)__builtin_amdgcn_raw_buffer_load_b16(rs, off, 0, 2);
 }
 
 // KP > 0 (the head-start launch, pcg.cpp): KP plain right-hand sides ride
@@ -281,10 +296,11 @@ __device__ __forceinline__ TmSlots<K> tm_slots(const OpArgs& a, int alt) {
     return s;
 }
 
-// XE: X's element type (double, or float for the _f32 entry points).  E counts
-// ROWS per lane per load either way: a float tile is read with loads of half
-// the width (8 bytes for E = 2), its descriptor's range and every byte offset
-// scaled by the element size, and the rows widened as they land.
+// XE: X's element type (double, float for the _f32 entry points, or uint16_t
+// for the _u16 ones: value k * 2^-16).  E counts ROWS per lane per load in every
+// case: a narrow tile is read with narrower loads (8 or 4 bytes for E = 2), its
+// descriptor's range and every byte offset scaled by the element size, and the
+// rows widened where they are used.
 template <int K, int S, int F, int L, int P, bool COMM, int E, bool FMA, int KP, class XE>
 __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t ld, int64_t N, int64_t M,
                                                const double* __restrict__ mave, const double* __restrict__ msig,
@@ -628,15 +644,16 @@ __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t
 #pragma unroll
             for (int e = 0; e < E; ++e) accp[k][s][e] = 0.0;
 
-    // A float tile's rows stay in the ring as loaded (xw, half the registers
+    // A narrow (float or 16-bit) tile's rows stay in the ring as loaded (xw, half the registers
     // of xr): dot() and finish() each widen and centre them where they use
     // them (the same operations on the same values: the same bits as the
     // centred copy a double tile keeps in xr), so a prefetched column is not
     // waited for by a conversion and the ring leaves the registers the
     // conversions need
-    constexpr bool F32 = XB == 4;
-    double xr[F32 ? 1 : RING][S][E];
-    float xw[F32 ? RING : 1][S][E];
+    constexpr bool NW = XB < 8;
+    typedef typename std::conditional<NW, XE, float>::type XW;
+    double xr[NW ? 1 : RING][S][E];
+    XW xw[NW ? RING : 1][S][E];
     double pk[RING];
     const char* xtile = reinterpret_cast<const char*>(X + mb * ld + r0);
     auto load = [&](int slot, int m) {
@@ -646,16 +663,16 @@ __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t
             __builtin_amdgcn_make_buffer_rsrc((void*)(xtile + c * ld * XB), (short)0, nbytes, 0x00020000);
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-            if constexpr (E == 2 && F32) {
-                const v2f x = tm_ld2<XE>(rs, (RS * s + jb) * XB);
+            if constexpr (E == 2 && NW) {
+                const xpair_t<XE> x = tm_ld2<XE>(rs, (RS * s + jb) * XB);
                 xw[slot][s][0] = x.x;
                 xw[slot][s][E - 1] = x.y;
             } else if constexpr (E == 2) {
                 const v2d x = tm_ld2<XE>(rs, (RS * s + jb) * XB);
                 xr[slot][s][0] = x.x;
                 xr[slot][s][E - 1] = x.y;
-            } else if constexpr (F32) {
-                xw[slot][s][0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (RS * s + jb) * 4, 0, 2));
+            } else if constexpr (NW) {
+                xw[slot][s][0] = tm_ld1<XE>(rs, (RS * s + jb) * XB);
             } else {
                 xr[slot][s][0] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, (RS * s + jb) * 8, 0, 2));
             }
@@ -682,8 +699,8 @@ __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t
             double dx[E], q[K][E];
 #pragma unroll
             for (int e = 0; e < E; ++e) {
-                if constexpr (F32) {
-                    dx[e] = (double)xw[slot][s][e] - me_;
+                if constexpr (NW) {
+                    dx[e] = widen1(xw[slot][s][e]) - me_;
                 } else {
                     dx[e] = xr[slot][s][e] - me_;
                     xr[slot][s][e] = dx[e];
@@ -767,18 +784,18 @@ __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t
                 cc[k] = sg * val;  // Ax: (x - mave) * (msig * x_i)
             }
         }
-        const double mu = F32 ? readlane_d(pk[slot], 0) : 0.0;
+        const double mu = NW ? readlane_d(pk[slot], 0) : 0.0;
 #pragma unroll
         for (int s = 0; s < S; ++s) {
             if (dbg & 8) break;
-            const double me_ = QFULL || valid[s] ? mu : 0.0;  // (a float tile: dot()'s centring again)
+            const double me_ = QFULL || valid[s] ? mu : 0.0;  // (a narrow tile: dot()'s centring again)
 #pragma unroll
             for (int k = 0; k < K; ++k)
 #pragma unroll
                 for (int e = 0; e < E; ++e) {
                     double dx;
-                    if constexpr (F32)
-                        dx = (double)xw[slot][s][e] - me_;
+                    if constexpr (NW)
+                        dx = widen1(xw[slot][s][e]) - me_;
                     else
                         dx = xr[slot][s][e];  // centred by dot()
                     if constexpr (FMA)
@@ -883,6 +900,15 @@ __global__ __launch_bounds__(kTmThreads) void atax_team_kernel_f32(const float* 
     atax_team_body<K, S, F, L, P, COMM, E, FMA, 0>(X, ld, N, M, mave, msig, a, T, TR, ilv, gate);
 }
 
+template <int K, int S, int F, int L, int P, bool COMM, int E, bool FMA>
+__global__ __launch_bounds__(kTmThreads) void atax_team_kernel_u16(const uint16_t* __restrict__ X, int64_t ld,
+                                                                   int64_t N, int64_t M,
+                                                                   const double* __restrict__ mave,
+                                                                   const double* __restrict__ msig, OpArgs a, int T,
+                                                                   int TR, int ilv, const int* __restrict__ gate) {
+    atax_team_body<K, S, F, L, P, COMM, E, FMA, 0>(X, ld, N, M, mave, msig, a, T, TR, ilv, gate);
+}
+
 // the head-start launch: one operator system (the Onsager solve's first CG
 // step) and kTmPlain plain right-hand sides (pcg.cpp)
 static constexpr int kTmPlain = kOpPlain;
@@ -897,6 +923,16 @@ __global__ __launch_bounds__(kTmThreads) void atax_team_plain_kernel(const doubl
 
 template <int S, int F, int L, int P, bool COMM, int E, bool FMA>
 __global__ __launch_bounds__(kTmThreads) void atax_team_plain_kernel_f32(const float* __restrict__ X, int64_t ld,
+                                                                         int64_t N, int64_t M,
+                                                                         const double* __restrict__ mave,
+                                                                         const double* __restrict__ msig, OpArgs a,
+                                                                         int T, int TR, int ilv,
+                                                                         const int* __restrict__ gate) {
+    atax_team_body<1, S, F, L, P, COMM, E, FMA, kTmPlain>(X, ld, N, M, mave, msig, a, T, TR, ilv, gate);
+}
+
+template <int S, int F, int L, int P, bool COMM, int E, bool FMA>
+__global__ __launch_bounds__(kTmThreads) void atax_team_plain_kernel_u16(const uint16_t* __restrict__ X, int64_t ld,
                                                                          int64_t N, int64_t M,
                                                                          const double* __restrict__ mave,
                                                                          const double* __restrict__ msig, OpArgs a,
@@ -925,7 +961,7 @@ __global__ __launch_bounds__(kTmThreads) void atax_team_plain_kernel_f32(const f
 #endif
 static constexpr int kAxTmF = AX_TEAM_F;  // columns prefetched (AX_TEAM_F: experiment builds)
 static constexpr int kAxTmMaxS = 4;    // loads per lane per column (1024-row steps)
-// (the body of ax_team_kernel and ax_team_kernel_f32: XE is X's element type)
+// (the body of ax_team_kernel, ax_team_kernel_f32 and ax_team_kernel_u16: XE is X's element type)
 template <int S, int KP, bool FU, class XE>
 __device__ __forceinline__ void ax_team_body(const XE* __restrict__ X, int64_t ld, int64_t N, int64_t M,
                                              const double* __restrict__ mave, const double* __restrict__ msig,
@@ -1047,6 +1083,15 @@ __global__ __launch_bounds__(kTmThreads) void ax_team_kernel_f32(const float* __
     ax_team_body<S, KP, FU>(X, ld, N, M, mave, msig, xs, part, fu, T, TR);
 }
 
+template <int S, int KP, bool FU>
+__global__ __launch_bounds__(kTmThreads) void ax_team_kernel_u16(const uint16_t* __restrict__ X, int64_t ld, int64_t N,
+                                                                 int64_t M, const double* __restrict__ mave,
+                                                                 const double* __restrict__ msig, CPtrs xs,
+                                                                 double* __restrict__ part, AxFuse fu, int T,
+                                                                 int TR) {
+    ax_team_body<S, KP, FU>(X, ld, N, M, mave, msig, xs, part, fu, T, TR);
+}
+
 // ---------------------------------------------------------------------------
 // host side: plans, instantiations, launch
 // ---------------------------------------------------------------------------
@@ -1102,16 +1147,20 @@ bool team_lds_layout(const OpPlan& pl, int64_t N, int K, int64_t out[6]) {
 // occ != null: no launch, *occ = the workgroups of this instantiation one CU
 // holds at once (hipOccupancyMaxActiveBlocksPerMultiprocessor).  PL: the
 // head-start kernel (K = 1 operator system + kTmPlain plain right-hand sides)
-// XE: the shard's element type (the _f32 entry points for float)
+// XE: the shard's element type (the _f32 entry points for float, the _u16 ones for uint16_t)
 template <int K, int S, int C, bool PL, class XE>
 static hipError_t launch_tm_e(const Shard& s, const OpPlan& pl, const OpArgs& a, hipStream_t st, const Timing& tm,
                               const int* gate, int* occ) {
     constexpr TmCfg c = kTmCfg[C];
     static_assert(!PL || K == 1, "the head-start kernel has one operator system");
-    constexpr bool F32 = sizeof(XE) == 4;
+    constexpr bool F32 = sizeof(XE) == 4, U16 = sizeof(XE) == 2;
     void (*kern)(const XE*, int64_t, int64_t, int64_t, const double*, const double*, OpArgs, int, int, int,
                  const int*);
-    if constexpr (PL && F32)
+    if constexpr (PL && U16)
+        kern = atax_team_plain_kernel_u16<S, c.F, c.L, c.P, c.comm, c.E, (bool)TM_FMA>;
+    else if constexpr (U16)
+        kern = atax_team_kernel_u16<K, S, c.F, c.L, c.P, c.comm, c.E, (bool)TM_FMA>;
+    else if constexpr (PL && F32)
         kern = atax_team_plain_kernel_f32<S, c.F, c.L, c.P, c.comm, c.E, (bool)TM_FMA>;
     else if constexpr (PL)
         kern = atax_team_plain_kernel<S, c.F, c.L, c.P, c.comm, c.E, (bool)TM_FMA>;
@@ -1139,6 +1188,7 @@ static hipError_t launch_tm_e(const Shard& s, const OpPlan& pl, const OpArgs& a,
 template <int K, int S, int C, bool PL>
 static hipError_t launch_tm(const Shard& s, const OpPlan& pl, const OpArgs& a, hipStream_t st, const Timing& tm,
                             const int* gate, int* occ) {
+    if (s.u16) return launch_tm_e<K, S, C, PL, uint16_t>(s, pl, a, st, tm, gate, occ);
     if (s.f32) return launch_tm_e<K, S, C, PL, float>(s, pl, a, st, tm, gate, occ);
     return launch_tm_e<K, S, C, PL, double>(s, pl, a, st, tm, gate, occ);
 }
@@ -1269,7 +1319,10 @@ bool ax_team_plan(int64_t N, int64_t M, int cus, AxPlan* out) {
 template <int S, int K, bool FU>
 static void launch_axt(const Shard& s, const AxPlan& pl, CPtrs x, double* part, hipStream_t st, const Timing& tm,
                        const AxFuse& fu) {
-    if (s.f32)
+    if (s.u16)
+        hipExtLaunchKernelGGL((ax_team_kernel_u16<S, K, FU>), dim3(pl.groups), dim3(kTmThreads), 0, st, tm.start,
+                              tm.stop, 0, s.x16(), s.ld, s.N, s.M, s.mave, s.msig, x, part, fu, pl.T, pl.TR);
+    else if (s.f32)
         hipExtLaunchKernelGGL((ax_team_kernel_f32<S, K, FU>), dim3(pl.groups), dim3(kTmThreads), 0, st, tm.start,
                               tm.stop, 0, s.x32(), s.ld, s.N, s.M, s.mave, s.msig, x, part, fu, pl.T, pl.TR);
     else
@@ -1315,10 +1368,10 @@ hipError_t ax_team(const Shard& s, const AxPlan& pl, int K, CPtrs x, double* par
     return hipGetLastError();
 }
 
-std::string ax_kernel_name(int K, bool fused, const AxPlan& pl, int f32) {
-    if (pl.T <= 0) return kernel_name(0, K, fused ? 1 : 0, pl.variant, f32);
+std::string ax_kernel_name(int K, bool fused, const AxPlan& pl, int ek) {
+    if (pl.T <= 0) return kernel_name(0, K, fused ? 1 : 0, pl.variant, ek);
     char b[96];
-    std::snprintf(b, sizeof b, "ax_team_kernel%s<%d, %d, %s>", f32 ? "_f32" : "", pl.S, K, fused ? "true" : "false");
+    std::snprintf(b, sizeof b, "ax_team_kernel%s<%d, %d, %s>", xe_suffix(ek), pl.S, K, fused ? "true" : "false");
     return b;
 }
 
@@ -1340,9 +1393,10 @@ bool team_plain_plan(int64_t N, int64_t M, int cus, const OpPlan& main, OpPlan* 
     return false;
 }
 
-int team_occupancy(const OpPlan& pl, int K, int f32) {
+int team_occupancy(const OpPlan& pl, int K, int ek) {
     int occ = 0;
-    const Shard s{nullptr, 0, (int64_t)pl.TR * pl.T, 1, nullptr, nullptr, f32};  // the LDS size needs TR and N only
+    // (the LDS size needs TR and N only)
+    const Shard s{nullptr, 0, (int64_t)pl.TR * pl.T, 1, nullptr, nullptr, ek == kXF32, ek == kXU16};
     const OpArgs a{};
     hipError_t e = hipErrorInvalidValue;
     switch (K) {
@@ -1354,9 +1408,9 @@ int team_occupancy(const OpPlan& pl, int K, int f32) {
     return e == hipSuccess ? occ : 0;
 }
 
-std::string team_kernel_name(int K, const OpPlan& pl, int f32) {
+std::string team_kernel_name(int K, const OpPlan& pl, int ek) {
     const TmCfg& c = kTmCfg[pl.cfg];
-    const char* sfx = f32 ? "_f32" : "";
+    const char* sfx = xe_suffix(ek);
     char b[128];
     if (K == 1 + kTmPlain)  // the head-start kernel
         std::snprintf(b, sizeof b, "atax_team_plain_kernel%s<%d, %d, %d, %d, %s, %d>", sfx, pl.S, c.F, c.L, c.P,

@@ -91,11 +91,17 @@ struct vampomi_ctx {
     uint64_t coll_seq = 0;  // collectives issued so far (divergence checks)
     bool aborted = false;   // comm_abort ran: no further collective
 
-    // M columns x ld, marker-major, pad rows zero: doubles, or floats with
-    // storage == VAMPOMI_STORE_F32 (fixed once X is allocated; rank-local: the
-    // ranks agree on nothing that depends on it)
+    // M columns x ld, marker-major, pad rows zero: doubles, floats with
+    // storage == VAMPOMI_STORE_F32, or 16-bit fixed point (uint16_t k, value
+    // k * 2^-16) with VAMPOMI_STORE_U16 (fixed once X is allocated; rank-local:
+    // the ranks agree on nothing that depends on it)
     void* X = nullptr;
     int storage = VAMPOMI_STORE_F64;
+    // U16 storage: what the last load's quantisation saw (vk::quantise_cols;
+    // zeroed when a load starts) and its host copy (vampomi_get_quant_stats)
+    vk::QuantRec* qrec = nullptr;
+    int64_t q_clamped = 0;
+    double q_max_err = 0.0;
     double* mave = nullptr;
     double* msig = nullptr;
     double* y = nullptr;     // ld, zero pad
@@ -172,8 +178,10 @@ struct vampomi_ctx {
     std::unique_ptr<IterWriter> writer;  // per-iteration output (writer.h), created with the context
 
     bool f32() const { return storage == VAMPOMI_STORE_F32; }
-    int64_t esize() const { return f32() ? 4 : 8; }  // bytes per element of X
-    vk::Shard shard() const { return vk::Shard{X, ld, N, M, mave, msig, f32() ? 1 : 0}; }
+    bool u16() const { return storage == VAMPOMI_STORE_U16; }
+    int ek() const { return u16() ? vk::kXU16 : f32() ? vk::kXF32 : vk::kXF64; }  // the element kind (kernels.h)
+    int64_t esize() const { return u16() ? 2 : f32() ? 4 : 8; }  // bytes per element of X
+    vk::Shard shard() const { return vk::Shard{X, ld, N, M, mave, msig, f32() ? 1 : 0, u16() ? 1 : 0}; }
     vampomi_ctx();   // defined in vamp.cpp, where VampRun is complete
     ~vampomi_ctx();
 };

@@ -814,11 +814,11 @@ static vampomi_status op_plan_local(vampomi_ctx* c) {
         // K; a device that cannot (or an occupancy query that failed) runs the
         // CG on the two-pass schedule instead
         for (int K = 1; K <= vk::kOpMaxK && op_ok; ++K) {
-            const int occ = vk::team_occupancy(c->opp, K, c->f32());
+            const int occ = vk::team_occupancy(c->opp, K, c->ek());
             if ((int64_t)occ * c->cus < c->opp.grid) {
                 std::fprintf(stderr, "libvampomi: one-pass operator off: %s fits %d workgroup(s) per CU; the plan "
                                      "needs %lld resident on %d CUs (two passes per CG step)\n",
-                             vk::team_kernel_name(K, c->opp, c->f32()).c_str(), occ, (long long)c->opp.grid, c->cus);
+                             vk::team_kernel_name(K, c->opp, c->ek()).c_str(), occ, (long long)c->opp.grid, c->cus);
                 op_ok = false;
             }
         }
@@ -826,7 +826,7 @@ static vampomi_status op_plan_local(vampomi_ctx* c) {
     // the head-start plan: optional (no plan, or a grid the device cannot
     // hold, only means the solves start without it)
     bool hs_ok = op_ok && vk::team_plain_plan(c->N, M, c->cus, c->opp, &c->opp_hs);
-    if (hs_ok && (int64_t)vk::team_occupancy(c->opp_hs, 1 + vk::kOpPlain, c->f32()) * c->cus < c->opp_hs.grid) hs_ok = false;
+    if (hs_ok && (int64_t)vk::team_occupancy(c->opp_hs, 1 + vk::kOpPlain, c->ek()) * c->cus < c->opp_hs.grid) hs_ok = false;
     c->op_ok_mine = op_ok;
     c->hs_ok_mine = hs_ok;
     if (!c->op_ts && std::getenv("VAMPOMI_OP_TS") && std::atoi(std::getenv("VAMPOMI_OP_TS"))) {
@@ -1127,6 +1127,8 @@ void release_ctx_resources(vampomi_ctx* c) {
     c->ev_pool.clear();
     if (c->X) (void)hipFree(c->X);
     c->X = nullptr;
+    if (c->qrec) (void)hipFree(c->qrec);
+    c->qrec = nullptr;
     for (double** p : {&c->mave, &c->msig, &c->y, &c->ax_part, &c->red_part, &c->scal, &c->nbuf, &c->mbuf,
                        &c->op_part, &c->op_nvec, &c->cov_Z, &c->cov_part, &c->cov_dev})
         dev_free(*p);
@@ -1175,8 +1177,10 @@ extern "C" vampomi_status vampomi_open(const vampomi_shard_desc* d, vampomi_ctx*
     if (const char* sv = std::getenv("VAMPOMI_STORAGE")) {  // the default storage (vampomi_set_storage)
         if (std::strcmp(sv, "f32") == 0)
             storage = VAMPOMI_STORE_F32;
+        else if (std::strcmp(sv, "u16") == 0)
+            storage = VAMPOMI_STORE_U16;
         else if (std::strcmp(sv, "f64") != 0)
-            return fail(VAMPOMI_ERR_ARG, std::string("VAMPOMI_STORAGE must be f32 or f64, not '") + sv + "'");
+            return fail(VAMPOMI_ERR_ARG, std::string("VAMPOMI_STORAGE must be f64, f32 or u16, not '") + sv + "'");
     }
     std::unique_ptr<vampomi_ctx> c(new vampomi_ctx());
     c->storage = storage;
@@ -1309,8 +1313,8 @@ static vampomi_status ensure_X(vampomi_ctx* c) {
 
 extern "C" vampomi_status vampomi_set_storage(vampomi_ctx* c, int storage) {
     if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
-    if (storage != VAMPOMI_STORE_F64 && storage != VAMPOMI_STORE_F32)
-        return fail(VAMPOMI_ERR_ARG, "storage must be VAMPOMI_STORE_F64 or VAMPOMI_STORE_F32");
+    if (storage != VAMPOMI_STORE_F64 && storage != VAMPOMI_STORE_F32 && storage != VAMPOMI_STORE_U16)
+        return fail(VAMPOMI_ERR_ARG, "storage must be VAMPOMI_STORE_F64, VAMPOMI_STORE_F32 or VAMPOMI_STORE_U16");
     if (c->X) return fail(VAMPOMI_ERR_STATE, "the storage is fixed once the methylation shard is allocated");
     c->storage = storage;
     return VAMPOMI_OK;
@@ -1334,11 +1338,66 @@ static vampomi_status finish_X(vampomi_ctx* c) {
     return VAMPOMI_OK;
 }
 
+// the bytes of one staging chunk of an ingest (256 MB; VAMPOMI_IO_CHUNK_BYTES:
+// tuning experiments, and tests of the chunk boundaries at small shapes)
+static int64_t io_chunk_bytes() {
+    const char* env = std::getenv("VAMPOMI_IO_CHUNK_BYTES");
+    const int64_t v = env ? std::atoll(env) : 0;
+    return v >= 4096 ? v : (int64_t)256 << 20;
+}
+
+// U16 storage: a load starts with the quantisation record zeroed (and the host
+// copy of the last one forgotten)
+static vampomi_status quant_begin(vampomi_ctx* c) {
+    c->q_clamped = 0;
+    c->q_max_err = 0.0;
+    if (!c->u16()) return VAMPOMI_OK;
+    if (!c->qrec && hipMalloc((void**)&c->qrec, sizeof(vk::QuantRec)) != hipSuccess) {
+        (void)hipGetLastError();
+        c->qrec = nullptr;
+        return fail(VAMPOMI_ERR_OOM, "quantisation record");
+    }
+    HIPCHK(hipMemsetAsync(c->qrec, 0, sizeof(vk::QuantRec), c->st));
+    HIPCHK(hipMemsetAsync(&c->qrec->first, 0xff, sizeof(unsigned long long), c->st));
+    return VAMPOMI_OK;
+}
+
+// ... and ends with the record read: rejected entries fail the load with
+// VAMPOMI_ERR_RANGE and leave the context without X
+static vampomi_status quant_end(vampomi_ctx* c) {
+    if (!c->u16() || !c->qrec) return VAMPOMI_OK;
+    vk::QuantRec r{};
+    HIPCHK(hipMemcpyAsync(&r, c->qrec, sizeof r, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    if (r.rejected) {
+        c->have_X = false;
+        const long long marker = (long long)(r.first / (unsigned long long)c->N);
+        const long long row = (long long)(r.first % (unsigned long long)c->N);
+        return fail(VAMPOMI_ERR_RANGE,
+                    std::to_string(r.rejected) + " methylation value(s) cannot be stored as 16-bit fixed point (NaN, "
+                    "infinite, below 0 or above 1); the first is marker " + std::to_string(marker) + ", row " +
+                    std::to_string(row));
+    }
+    c->q_clamped = (int64_t)r.clamped;
+    std::memcpy(&c->q_max_err, &r.max_err, sizeof(double));
+    return VAMPOMI_OK;
+}
+
+extern "C" vampomi_status vampomi_get_quant_stats(const vampomi_ctx* c, int64_t* clamped, double* max_abs_err) {
+    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
+    if (!c->have_X) return fail(VAMPOMI_ERR_STATE, "no methylation data loaded");
+    if (clamped) *clamped = c->q_clamped;
+    if (max_abs_err) *max_abs_err = c->q_max_err;
+    return VAMPOMI_OK;
+}
+
 // Columns [i0, i0 + nc) of the shard from a host block of nc columns of
-// elements of in_es bytes (8: doubles, 4: floats), column stride ld_in
-// elements.  The same element type as the storage: a strided copy into the
-// padded layout.  Otherwise the block is staged on the device as it is and
-// converted there (vk::narrow_cols, nearest even / vk::widen_cols, exact):
+// elements of in_es bytes (8: doubles, 4: floats, 2: 16-bit fixed point),
+// column stride ld_in elements.  The same element type as the storage: a
+// strided copy into the padded layout.  Otherwise the block is staged on the
+// device as it is and converted there (vk::narrow_cols, nearest even /
+// vk::widen_cols and vk::dequant_cols, exact / vk::quantise_cols, nearest even
+// on the 2^-16 grid, range-checked into c->qrec):
 // *stage (cap_bytes; grown as needed, freed by the caller) is that buffer.  All
 // on the context's stream, so the caller may reuse src once the stream has
 // passed this point.
@@ -1366,25 +1425,37 @@ static vampomi_status put_cols(vampomi_ctx* c, int64_t i0, int64_t nc, const voi
     }
     HIPCHK(hipMemcpy2DAsync(*stage, (size_t)c->N * in_es, src, (size_t)ld_in * in_es, (size_t)c->N * in_es,
                             (size_t)nc, hipMemcpyHostToDevice, c->st));
-    if (in_es == 8)
+    if (es == 2 && in_es == 8)
+        HIPCHK(vk::quantise_cols((const double*)*stage, c->N, c->N, nc, (uint16_t*)dst, c->ld, c->S + i0, c->qrec,
+                                 c->st));
+    else if (es == 2)
+        HIPCHK(vk::quantise_cols((const float*)*stage, c->N, c->N, nc, (uint16_t*)dst, c->ld, c->S + i0, c->qrec,
+                                 c->st));
+    else if (in_es == 2 && es == 8)
+        HIPCHK(vk::dequant_cols((const uint16_t*)*stage, c->N, c->N, nc, (double*)dst, c->ld, c->st));
+    else if (in_es == 2)
+        HIPCHK(vk::dequant_cols((const uint16_t*)*stage, c->N, c->N, nc, (float*)dst, c->ld, c->st));
+    else if (in_es == 8)
         HIPCHK(vk::narrow_cols((const double*)*stage, c->N, c->N, nc, (float*)dst, c->ld, c->st));
     else
         HIPCHK(vk::widen_cols((const float*)*stage, c->N, c->N, nc, (double*)dst, c->ld, c->st));
     return VAMPOMI_OK;
 }
 
-// a host shard of doubles (in_es 8) or floats (4), in chunks of about 256 MB
-// where it has to be converted (put_cols' staging buffer)
+// a host shard of doubles (in_es 8), floats (4) or 16-bit fixed point (2), in
+// chunks of about 256 MB where it has to be converted (put_cols' staging
+// buffer)
 static vampomi_status load_host(vampomi_ctx* c, const void* X, int64_t ld_in, int in_es) {
     if (!c || (!X && c->M > 0) || ld_in < c->N) return fail(VAMPOMI_ERR_ARG, "invalid host shard");
     HIPCHK(hipSetDevice(c->device));
     STCHK(ensure_X(c));
+    STCHK(quant_begin(c));
     void* stage = nullptr;
     size_t cap = 0;
     vampomi_status st = VAMPOMI_OK;
     const int64_t chunk = (int64_t)in_es == c->esize()
                               ? std::max<int64_t>(c->M, 1)
-                              : std::max<int64_t>(1, ((int64_t)256 << 20) / (c->N * in_es));
+                              : std::max<int64_t>(1, io_chunk_bytes() / (c->N * in_es));
     for (int64_t i0 = 0; i0 < c->M && st == VAMPOMI_OK; i0 += chunk)
         st = put_cols(c, i0, std::min(chunk, c->M - i0), (const char*)X + (size_t)i0 * (size_t)ld_in * in_es, ld_in,
                       in_es, &stage, &cap);
@@ -1393,11 +1464,16 @@ static vampomi_status load_host(vampomi_ctx* c, const void* X, int64_t ld_in, in
         (void)hipFree(stage);
     }
     if (st != VAMPOMI_OK) return st;
+    STCHK(quant_end(c));
     return finish_X(c);
 }
 
 extern "C" vampomi_status vampomi_load_meth_host(vampomi_ctx* c, const double* X, int64_t ld_in) {
     return load_host(c, X, ld_in, 8);
+}
+
+extern "C" vampomi_status vampomi_load_meth_host_u16(vampomi_ctx* c, const uint16_t* X, int64_t ld_in) {
+    return load_host(c, X, ld_in, 2);
 }
 
 extern "C" vampomi_status vampomi_load_meth_host_f32(vampomi_ctx* c, const float* X, int64_t ld_in) {
@@ -1432,8 +1508,9 @@ static bool pread_parallel(int fd, char* dst, size_t want, off_t off, int nt) {
 }
 
 // read_methylation_data (src/data.cpp:116-153): this rank's M*N elements of
-// in_es bytes (8: the reference's doubles; 4: floats in the same marker-major
-// layout) at byte offset S*N*in_es (64-bit offsets: the reference's int i*N
+// in_es bytes (8: the reference's doubles; 4: floats, 2: little-endian uint16
+// k meaning k * 2^-16, in the same marker-major layout) at byte offset
+// S*N*in_es (64-bit offsets: the reference's int i*N
 // overflows past 2^31 elements), streamed through three pinned 256 MB staging
 // buffers: the parallel read of chunk k+1 overlaps the host-to-device copy of
 // chunk k, which lands directly in the ld-padded column layout, or, where the
@@ -1449,8 +1526,12 @@ static vampomi_status load_file(vampomi_ctx* c, const char* path, int in_es) {
         ::close(fd);
         return s0;
     }
+    if (const vampomi_status s0 = quant_begin(c)) {
+        ::close(fd);
+        return s0;
+    }
     const size_t colb = (size_t)c->N * (size_t)in_es;
-    const size_t chunk_cols = std::max<size_t>(1, ((size_t)256 << 20) / colb);
+    const size_t chunk_cols = std::max<size_t>(1, (size_t)io_chunk_bytes() / colb);
     const char* env = std::getenv("VAMPOMI_IO_THREADS");
     const int nt = env ? std::max(1, std::atoi(env)) : (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
     constexpr int NB = 3;
@@ -1497,6 +1578,7 @@ static vampomi_status load_file(vampomi_ctx* c, const char* path, int in_es) {
     if (stage) (void)hipFree(stage);
     ::close(fd);
     if (st != VAMPOMI_OK) return st;
+    STCHK(quant_end(c));
     return finish_X(c);
 }
 
@@ -1506,11 +1588,43 @@ extern "C" vampomi_status vampomi_load_meth_file_f32(vampomi_ctx* c, const char*
     return load_file(c, path, 4);
 }
 
+extern "C" vampomi_status vampomi_load_meth_file_u16(vampomi_ctx* c, const char* path) {
+    return load_file(c, path, 2);
+}
+
 extern "C" vampomi_status vampomi_generate_meth(vampomi_ctx* c, uint64_t seed, int kind) {
     if (!c || (kind != VAMPOMI_GEN_GAUSS && kind != VAMPOMI_GEN_METH)) return fail(VAMPOMI_ERR_ARG, "bad argument");
+    if (c->u16() && kind == VAMPOMI_GEN_GAUSS)
+        return fail(VAMPOMI_ERR_RANGE, "VAMPOMI_GEN_GAUSS values are not in [0, 1]: they cannot be stored as 16-bit "
+                                       "fixed point (VAMPOMI_STORE_U16)");
     HIPCHK(hipSetDevice(c->device));
     STCHK(ensure_X(c));
-    HIPCHK(vk::gen_markers(seed, kind, c->N, c->ld, c->S, c->M, c->X, c->f32() ? 1 : 0, c->st));
+    STCHK(quant_begin(c));
+    if (!c->u16()) {
+        HIPCHK(vk::gen_markers(seed, kind, c->N, c->ld, c->S, c->M, c->X, c->ek(), c->st));
+        return finish_X(c);
+    }
+    // U16: the generator's doubles in chunks of columns (about 256 MB), each
+    // quantised into the shard as an ingest of the fp64 matrix would be
+    const int64_t chunk = std::min<int64_t>(std::max<int64_t>(c->M, 1),
+                                            std::max<int64_t>(1, io_chunk_bytes() / (c->ld * 8)));
+    void* stage = nullptr;
+    if (hipMalloc(&stage, (size_t)chunk * (size_t)c->ld * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VAMPOMI_ERR_OOM, "device staging buffer of the generator");
+    }
+    hipError_t e = hipSuccess;
+    for (int64_t i0 = 0; i0 < c->M && e == hipSuccess; i0 += chunk) {
+        const int64_t nc = std::min(chunk, c->M - i0);
+        e = vk::gen_markers(seed, kind, c->N, c->ld, c->S + i0, nc, stage, vk::kXF64, c->st);
+        if (e == hipSuccess)
+            e = vk::quantise_cols((const double*)stage, c->ld, c->N, nc, (uint16_t*)c->X + i0 * c->ld, c->ld,
+                                  c->S + i0, c->qrec, c->st);
+    }
+    (void)hipStreamSynchronize(c->st);
+    (void)hipFree(stage);
+    if (e != hipSuccess) return fail(VAMPOMI_ERR_HIP, std::string("generate_meth: ") + hipGetErrorString(e));
+    STCHK(quant_end(c));
     return finish_X(c);
 }
 
@@ -1564,19 +1678,22 @@ extern "C" vampomi_status vampomi_read_markers(vampomi_ctx* c, int64_t i0, int64
     if (!c || !out || i0 < 0 || count < 0 || i0 + count > c->M) return fail(VAMPOMI_ERR_ARG, "bad marker range");
     if (!c->have_X) return fail(VAMPOMI_ERR_STATE, "no methylation data loaded");
     HIPCHK(hipSetDevice(c->device));
-    if (count > 0 && !c->f32())
+    const bool narrow = c->f32() || c->u16();
+    if (count > 0 && !narrow)
         HIPCHK(hipMemcpy2DAsync(out, (size_t)c->N * 8, (const double*)c->X + i0 * c->ld, (size_t)c->ld * 8,
                                 (size_t)c->N * 8, (size_t)count, hipMemcpyDeviceToHost, c->st));
-    // fp32 storage: the stored floats widened on the device (exact), in chunks
-    // of about 64 MB through a staging buffer
+    // fp32 / 16-bit storage: the stored values widened on the device (exact),
+    // in chunks of about 64 MB through a staging buffer
     void* stage = nullptr;
-    if (count > 0 && c->f32()) {
+    if (count > 0 && narrow) {
         const int64_t chunk = std::min<int64_t>(count, std::max<int64_t>(1, ((int64_t)64 << 20) / (c->N * 8)));
         HIPCHK(hipMalloc(&stage, (size_t)chunk * (size_t)c->N * 8));
         for (int64_t k = 0; k < count; k += chunk) {
             const int64_t nc = std::min(chunk, count - k);
-            hipError_t e = vk::widen_cols((const float*)c->X + (i0 + k) * c->ld, c->ld, c->N, nc, (double*)stage,
-                                          c->N, c->st);
+            hipError_t e = c->u16() ? vk::dequant_cols((const uint16_t*)c->X + (i0 + k) * c->ld, c->ld, c->N, nc,
+                                                       (double*)stage, c->N, c->st)
+                                    : vk::widen_cols((const float*)c->X + (i0 + k) * c->ld, c->ld, c->N, nc,
+                                                     (double*)stage, c->N, c->st);
             if (e == hipSuccess)
                 e = hipMemcpyAsync(out + k * c->N, stage, (size_t)nc * (size_t)c->N * 8, hipMemcpyDeviceToHost, c->st);
             if (e != hipSuccess) {
@@ -2163,7 +2280,7 @@ extern "C" vampomi_status vampomi_dev_op_lds(int64_t N, int64_t M, int cus, int 
 extern "C" vampomi_status vampomi_dev_mem_plan_storage(int64_t N, int64_t Mt, int nranks, int rank, int cus,
                                                        int probit, int writer, int storage, int64_t* bytes) {
     if (!bytes || N < 2 || Mt < nranks || nranks < 1 || rank < 0 || rank >= nranks || cus < 1 ||
-        (storage != VAMPOMI_STORE_F64 && storage != VAMPOMI_STORE_F32))
+        (storage != VAMPOMI_STORE_F64 && storage != VAMPOMI_STORE_F32 && storage != VAMPOMI_STORE_U16))
         return fail(VAMPOMI_ERR_ARG, "bad argument");
     int64_t M = 0, S = 0, Mm = 0;
     vampomi_divide_work(Mt, nranks, rank, &M, &S, &Mm);
@@ -2204,6 +2321,7 @@ extern "C" vampomi_status vampomi_dev_mem_plan_storage(int64_t N, int64_t Mt, in
     // is the fp64 plan less exactly that saving (the allocator's rounding of
     // the smaller block is not modelled: at most one granule either way)
     if (storage == VAMPOMI_STORE_F32) total -= Mx * ld * 4;
+    if (storage == VAMPOMI_STORE_U16) total -= Mx * ld * 6;  // (two bytes per element)
     *bytes = total;
     return VAMPOMI_OK;
 }
@@ -2222,9 +2340,9 @@ static std::string op_name(const vampomi_ctx* c, int K) {
     if (K == 1 + vk::kOpPlain) {  // the head-start launch
         vk::OpPlan h{};
         if (!vk::team_plain_plan(c->N, std::max<int64_t>(c->M, 1), cus, p, &h)) return "(no head-start plan)";
-        return vk::team_kernel_name(K, h, c->f32());
+        return vk::team_kernel_name(K, h, c->ek());
     }
-    return vk::op_kernel_name(K, p, c->f32());
+    return vk::op_kernel_name(K, p, c->ek());
 }
 
 extern "C" vampomi_status vampomi_dev_read_ceiling(vampomi_ctx* c, int reps, double* us_med, double* bytes,
@@ -2242,13 +2360,13 @@ extern "C" vampomi_status vampomi_dev_read_ceiling(vampomi_ctx* c, int reps, dou
     int best_kind = -1;
     for (int kind = 0; kind < 2; ++kind) {
         double nb = 0.0;
-        if (vk::stream_read(c->X, c->f32(), n, kind, c->cus, c->st, vk::Timing{}, c->red_part, &nb) != hipSuccess) {
+        if (vk::stream_read(c->X, c->ek(), n, kind, c->cus, c->st, vk::Timing{}, c->red_part, &nb) != hipSuccess) {
             (void)hipGetLastError();
             continue;  // the buffer is too small for this shape
         }
         std::vector<float> ms((size_t)reps);
         for (int r = 0; r < reps; ++r) {
-            HIPCHK(vk::stream_read(c->X, c->f32(), n, kind, c->cus, c->st, vk::Timing{a, b}, c->red_part, &nb));
+            HIPCHK(vk::stream_read(c->X, c->ek(), n, kind, c->cus, c->st, vk::Timing{a, b}, c->red_part, &nb));
             HIPCHK(hipEventSynchronize(b));
             HIPCHK(hipEventElapsedTime(&ms[(size_t)r], a, b));
         }
@@ -2273,11 +2391,11 @@ extern "C" vampomi_status vampomi_dev_kernel_name(const vampomi_ctx* c, int whic
                                                   int cap) {
     if (!c || !out || cap < 1) return fail(VAMPOMI_ERR_ARG, "bad argument");
     // which = 3: mode carries N (the operator's instantiation depends on it)
-    const int f32 = c->f32();
-    const std::string n = which == 2   ? vk::loo_kernel_name(c->loo_variant, f32)
+    const int ek = c->ek();  // the element kind: the suffix of the entry points
+    const std::string n = which == 2   ? vk::loo_kernel_name(c->loo_variant, ek)
                           : which == 3 ? op_name(c, K)
-                          : which == 0 ? vk::ax_kernel_name(K, mode == 1, c->axp, f32)
-                                       : vk::kernel_name(1, K, mode, c->atx_variant, f32);
+                          : which == 0 ? vk::ax_kernel_name(K, mode == 1, c->axp, ek)
+                                       : vk::kernel_name(1, K, mode, c->atx_variant, ek);
     std::snprintf(out, (size_t)cap, "%s", n.c_str());
     return VAMPOMI_OK;
 }

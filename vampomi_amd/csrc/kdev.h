@@ -11,13 +11,17 @@ namespace vk {
 
 typedef double v2d __attribute__((ext_vector_type(2)));
 typedef float v2f __attribute__((ext_vector_type(2)));
+typedef uint16_t v2h __attribute__((ext_vector_type(2)));  // (a ushort2: two fixed-point rows in one dword)
 
-// A row pair of a column of X: one 16-byte load of a double column, or one
-// 8-byte load of a float column.  The lane owns the same two rows either way,
-// so every sum over a column runs in the same order for both storages.  The
-// pair stays as loaded (xpair_t) until it is used and is widened there
-// (widen: exact; nothing for doubles), so a load issued ahead is not waited
-// for by a conversion.  NT: nontemporal (the streaming passes)
+// A row pair of a column of X: one 16-byte load of a double column, one
+// 8-byte load of a float column, or one 4-byte load of a 16-bit fixed-point
+// column (uint16_t k, value k * 2^-16).  The lane owns the same two rows in
+// every case, so every sum over a column runs in the same order for all
+// storages.  The pair stays as loaded (xpair_t) until it is used and is widened
+// there (widen: exact; nothing for doubles; (double)k * 2^-16 is an exact
+// product, a power-of-two scaling of an integer below 2^16), so a load issued
+// ahead is not waited for by a conversion.  NT: nontemporal (the streaming
+// passes)
 template <class E>
 struct XPair;
 template <>
@@ -27,6 +31,10 @@ struct XPair<double> {
 template <>
 struct XPair<float> {
     typedef v2f type;
+};
+template <>
+struct XPair<uint16_t> {
+    typedef v2h type;
 };
 template <class E>
 using xpair_t = typename XPair<E>::type;
@@ -38,6 +46,11 @@ __device__ __forceinline__ xpair_t<E> ldx(const E* p) {
 }
 __device__ __forceinline__ v2d widen(v2d x) { return x; }
 __device__ __forceinline__ v2d widen(v2f x) { return v2d{(double)x.x, (double)x.y}; }
+__device__ __forceinline__ v2d widen(v2h x) { return v2d{(double)x.x * 0x1p-16, (double)x.y * 0x1p-16}; }
+// one stored element widened (the team operator keeps single rows in its ring)
+__device__ __forceinline__ double widen1(double x) { return x; }
+__device__ __forceinline__ double widen1(float x) { return (double)x; }
+__device__ __forceinline__ double widen1(uint16_t x) { return (double)x * 0x1p-16; }
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

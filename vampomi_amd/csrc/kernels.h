@@ -38,18 +38,27 @@ struct Ptrs { double* p[kMaxRhs]; };
 
 // The device-resident marker shard: M columns (markers) of N samples, column
 // stride ld >= N elements (ld % 16 == 0, pad rows zero), plus marker stats.
-// The elements are doubles, or floats with f32 set (VAMPOMI_STORE_F32): every
-// kernel that reads X has an entry point per element type (the fp32 ones with
-// an _f32 suffix) over one body; a lane owns the same rows either way and
-// widens what it loads, so both storages sum in the same order.
+// The elements are doubles, floats with f32 set (VAMPOMI_STORE_F32), or 16-bit
+// fixed point with u16 set (VAMPOMI_STORE_U16: uint16_t k, value k * 2^-16):
+// every kernel that reads X has an entry point per element type (the narrow
+// ones with an _f32 / _u16 suffix) over one body; a lane owns the same rows in
+// every case and widens what it loads (exactly), so all storages sum in the
+// same order.
+// The element kind where a plain int names it (kernel names, occupancy,
+// gen_markers, stream_read): kXF64, kXF32, kXU16.
+enum { kXF64 = 0, kXF32 = 1, kXU16 = 2 };
+inline const char* xe_suffix(int ek) { return ek == kXU16 ? "_u16" : ek == kXF32 ? "_f32" : ""; }
 struct Shard {
     const void* X;
     int64_t ld, N, M;
     const double* mave;
     const double* msig;
     int f32 = 0;
+    int u16 = 0;
     const double* x64() const { return static_cast<const double*>(X); }
     const float* x32() const { return static_cast<const float*>(X); }
+    const uint16_t* x16() const { return static_cast<const uint16_t*>(X); }
+    int ek() const { return u16 ? kXU16 : f32 ? kXF32 : kXF64; }
 };
 
 // ---- A.x : two-stage, deterministic --------------------------------------
@@ -103,16 +112,19 @@ hipError_t ax_partial(const Shard& s, const AxPlan& pl, int K, CPtrs x, double* 
 // A pure read stream of x[0, n) (the read ceiling, vampomi_dev_read_ceiling):
 // kind 0 lockstep 8-wave workgroups (cus of them), kind 1 a 1 MiB chunk per
 // wave; returns the bytes read in *bytes (whole units of 1024 / 2^17
-// elements).  f32: x holds floats, read with the 8-byte loads of the fp32
-// kernels (the ceiling of the bytes actually resident)
-hipError_t stream_read(const void* x, int f32, int64_t n, int kind, int cus, hipStream_t st, const Timing& tm,
+// elements).  ek (kXF64 / kXF32 / kXU16) is x's element kind: floats are read
+// with the 8-byte loads of the fp32 kernels; 16-bit elements with 16-byte loads
+// over the resident bytes (a pure read is tied to no summation order, so it
+// need not keep the operators' rows per lane; n a multiple of 8 elements).
+// Either way the ceiling of the bytes actually resident
+hipError_t stream_read(const void* x, int ek, int64_t n, int kind, int cus, hipStream_t st, const Timing& tm,
                        double* sink, double* bytes);
 // the team plan (atax_team.hip): false if N has none (rows per member past 4
 // loads per lane of 1024-row steps at every team size)
 bool ax_team_plan(int64_t N, int64_t M, int cus, AxPlan* out);
 hipError_t ax_team(const Shard& s, const AxPlan& pl, int K, CPtrs x, double* part, hipStream_t st, const Timing& tm,
                    const AxFuse& fu);
-std::string ax_kernel_name(int K, bool fused, const AxPlan& pl, int f32 = 0);  // as rocprofv3 prints it
+std::string ax_kernel_name(int K, bool fused, const AxPlan& pl, int ek = 0);  // as rocprofv3 prints it
 // out_k[j] = sum_c part[c][k][j]; if div > 0 then out_k[j] /= div
 hipError_t ax_reduce(const AxPlan& pl, int K, int64_t N, int64_t ld, const double* part, Ptrs out,
                      double div, hipStream_t st, const int* gate = nullptr);
@@ -125,7 +137,7 @@ hipError_t vec_div(int K, int64_t n, int64_t ld, Ptrs v, double div, hipStream_t
 // mode 1 (lmmse_mult): out_k[i] = ((msig_i*dot)*scale)*tau + gam2*p_k[i]
 // (<out_k, p_k> is a separate fixed-geometry reduction); gate as in AxFuse
 int atx_blocks(int64_t M, int K, int variant);
-std::string kernel_name(int which, int K, int mode, int variant, int f32 = 0);  // as rocprofv3 prints it
+std::string kernel_name(int which, int K, int mode, int variant, int ek = 0);  // as rocprofv3 prints it
 // zf/beta (mode 1, may be null): the epilogue's p_k is zf_k + beta[k]*p_k;
 // sraw (mode 1, may be null): also stores the raw product (msig_i*dot)*scale
 hipError_t atx(const Shard& s, int K, CPtrs u, Ptrs out, double scale, int mode, double tau,
@@ -243,13 +255,13 @@ struct OpArgs {
     OpAlt alt;    // team kernels only, never with fold.on or plain right-hand sides
 };
 static_assert(sizeof(OpAlt::tab) / sizeof(OpAlt::Slot) == kOpMaxK + 1, "one entry per system and the alternate's");
-std::string op_kernel_name(int K, const OpPlan& pl, int f32 = 0);
-std::string team_kernel_name(int K, const OpPlan& pl, int f32 = 0);
+std::string op_kernel_name(int K, const OpPlan& pl, int ek = 0);
+std::string team_kernel_name(int K, const OpPlan& pl, int ek = 0);
 // workgroups of the team kernel of plan pl (T >= 1) with K right-hand sides one
 // CU holds at once (0: it cannot run); a plan needs grid <= this x CUs, since
-// a team launch needs all its workgroups resident together (f32: of the fp32
-// entry point)
-int team_occupancy(const OpPlan& pl, int K, int f32 = 0);
+// a team launch needs all its workgroups resident together (ek: of that
+// element kind's entry point)
+int team_occupancy(const OpPlan& pl, int K, int ek = 0);
 hipError_t atax(const Shard& s, const OpPlan& pl, int K, const OpArgs& a, hipStream_t st, const Timing& tm = Timing{},
                 const int* gate = nullptr);
 hipError_t atax_team(const Shard& s, const OpPlan& pl, int K, const OpArgs& a, hipStream_t st, const Timing& tm,
@@ -271,8 +283,10 @@ hipError_t marker_stats(const Shard& s, double nonas, double alpha_scale, double
                         hipStream_t st);
 
 // ---- synthetic data --------------------------------------------------------
-// (f32: X holds floats and receives the generator's value rounded to nearest even)
-hipError_t gen_markers(uint64_t seed, int kind, int64_t N, int64_t ld, int64_t S, int64_t M, void* X, int f32,
+// (ek kXF32: X holds floats and receives the generator's value rounded to
+// nearest even; kXU16 is not generated in place: the engine quantises staged
+// fp64 chunks, quantise_cols)
+hipError_t gen_markers(uint64_t seed, int kind, int64_t N, int64_t ld, int64_t S, int64_t M, void* X, int ek,
                        hipStream_t st);
 // ---- fp32 storage: conversions between a staged fp64 chunk and the shard -------
 // dst[c*ldd + j] = (float)src[c*lds + j] (nearest even), j < N, c < ncols
@@ -281,6 +295,29 @@ hipError_t narrow_cols(const double* src, int64_t lds, int64_t N, int64_t ncols,
 // dst[c*ldd + j] = (double)src[c*lds + j] (exact)
 hipError_t widen_cols(const float* src, int64_t lds, int64_t N, int64_t ncols, double* dst, int64_t ldd,
                       hipStream_t st);
+// ---- 16-bit fixed-point storage (uint16_t k, value k * 2^-16) ----------------
+// What quantise_cols has seen since the record was zeroed (device memory, 4
+// words): every field is an integer sum, a minimum or a maximum, so none
+// depends on the order the launches' threads ran in.
+struct QuantRec {
+    unsigned long long rejected;  // entries that are NaN, infinite, < 0 or > 1
+    unsigned long long first;     // the smallest index (col0 + c) * N + j of a rejected entry (~0: none)
+    unsigned long long clamped;   // accepted entries that rounded to 65536 and were stored as 65535
+    unsigned long long max_err;   // max |k * 2^-16 - x| over the accepted entries, as the bits of that double
+};
+// dst[c*ldd + j] = min(65535, rint(src[c*lds + j] * 65536)) (ties to even; the
+// product is exact), j < N, c < ncols, for 0 <= x <= 1 (-0.0 is 0); any other
+// entry stores 0 and is counted in *rec.  XS: double or float (widened first).
+// col0: the index of column 0, for rec->first
+hipError_t quantise_cols(const double* src, int64_t lds, int64_t N, int64_t ncols, uint16_t* dst, int64_t ldd,
+                         int64_t col0, QuantRec* rec, hipStream_t st);
+hipError_t quantise_cols(const float* src, int64_t lds, int64_t N, int64_t ncols, uint16_t* dst, int64_t ldd,
+                         int64_t col0, QuantRec* rec, hipStream_t st);
+// dst[c*ldd + j] = src[c*lds + j] * 2^-16 (exact, as a double and as a float)
+hipError_t dequant_cols(const uint16_t* src, int64_t lds, int64_t N, int64_t ncols, double* dst, int64_t ldd,
+                        hipStream_t st);
+hipError_t dequant_cols(const uint16_t* src, int64_t lds, int64_t N, int64_t ncols, float* dst, int64_t ldd,
+                        hipStream_t st);
 // beta_i = gauss(seed) for causal markers (uniform < lam), else 0; the count
 // of causal markers in ro.out[0]
 hipError_t gen_beta(uint64_t seed, double lam, int64_t S, int64_t M, double* beta, const RedOut& ro, hipStream_t st);
@@ -512,7 +549,7 @@ hipError_t cov_offset(int64_t N, int C, const double* Z, int64_t ld, const doubl
 // samples of marker j (RAW X), ym = ymod + X / sqrtN * x1[j]  (data::pvals_loo)
 hipError_t loo_sums(const Shard& s, const double* ymod, const double* x1, double sqrtN, double* stats,
                     hipStream_t st, int variant = kLooDefault, const Timing& tm = Timing{});
-std::string loo_kernel_name(int variant, int f32 = 0);
+std::string loo_kernel_name(int variant, int ek = 0);
 int loo_variant_count();
 bool loo_variant_ok(int v);
 // pvals[j] = linear_reg1d_pvals(stats[5j..5j+4], n)  (src/utilities.cpp:269-282)

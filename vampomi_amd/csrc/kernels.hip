@@ -342,7 +342,7 @@ __device__ __forceinline__ void ax_zero(double (&acc)[K][R]) {
         for (int r = 0; r < R; ++r) acc[k][r] = 0.0;
 }
 
-// (the body of ax_partial_kernel and ax_partial_kernel_f32: XE is X's element type)
+// (the body of ax_partial_kernel, ax_partial_kernel_f32 and ax_partial_kernel_u16: XE is X's element type)
 template <int K, int R, int U, bool NT, bool FU, class XE>
 __device__ __forceinline__ void ax_partial_body(const XE* __restrict__ X, int64_t ld, int64_t N, int64_t M,
                                                 const double* __restrict__ mave,
@@ -426,6 +426,16 @@ __global__ __launch_bounds__(kBlock) void ax_partial_kernel_f32(const float* __r
     ax_partial_body<K, R, U, NT, FU>(X, ld, N, M, mave, msig, xs, tiles, span, nband, part, fu);
 }
 
+template <int K, int R, int U, bool NT, bool FU>
+__global__ __launch_bounds__(kBlock) void ax_partial_kernel_u16(const uint16_t* __restrict__ X, int64_t ld,
+                                                                int64_t N, int64_t M,
+                                                                const double* __restrict__ mave,
+                                                                const double* __restrict__ msig, CPtrs xs,
+                                                                int64_t tiles, int64_t span, int64_t nband,
+                                                                double* __restrict__ part, AxFuse fu) {
+    ax_partial_body<K, R, U, NT, FU>(X, ld, N, M, mave, msig, xs, tiles, span, nband, part, fu);
+}
+
 // tuning table (rows per lane R, markers in flight U, nontemporal loads)
 struct AxVariant { int R, U; bool NT; };
 static constexpr AxVariant kAxVariants[] = {
@@ -488,6 +498,17 @@ AxPlan ax_plan_for(int64_t N, int64_t M, int cus, int variant) {
 template <int K, int R, int U, bool NT>
 static void launch_ax(const Shard& s, const AxPlan& pl, CPtrs x, double* part, hipStream_t st, const Timing& tm,
                       const AxFuse& fu) {
+    if (s.u16) {
+        if (fu.z.p[0])
+            hipExtLaunchKernelGGL((ax_partial_kernel_u16<K, R, U, NT, true>), dim3(pl.groups), dim3(kBlock), 0, st,
+                                  tm.start, tm.stop, 0, s.x16(), s.ld, s.N, s.M, s.mave, s.msig, x, pl.tiles,
+                                  pl.span, pl.nband, part, fu);
+        else
+            hipExtLaunchKernelGGL((ax_partial_kernel_u16<K, R, U, NT, false>), dim3(pl.groups), dim3(kBlock), 0, st,
+                                  tm.start, tm.stop, 0, s.x16(), s.ld, s.N, s.M, s.mave, s.msig, x, pl.tiles,
+                                  pl.span, pl.nband, part, fu);
+        return;
+    }
     if (s.f32) {
         if (fu.z.p[0])
             hipExtLaunchKernelGGL((ax_partial_kernel_f32<K, R, U, NT, true>), dim3(pl.groups), dim3(kBlock), 0, st,
@@ -638,6 +659,15 @@ __global__ __launch_bounds__(512) void stream_lock_kernel_f32(const float* __res
     stream_lock_body(x, units, never, sink);
 }
 
+// 16-bit elements: the resident bytes as 16-byte loads (units of 8 KiB, the
+// double kernel's).  A pure read is tied to no summation order, so it does not
+// keep the operators' two rows per lane; the words are summed as the bit
+// patterns they are, which nothing ever reads.
+__global__ __launch_bounds__(512) void stream_lock_kernel_u16(const uint16_t* __restrict__ x, int64_t units,
+                                                              double never, double* __restrict__ sink) {
+    stream_lock_body(reinterpret_cast<const double*>(x), units, never, sink);
+}
+
 template <class XE>
 __device__ __forceinline__ void stream_chunk_body(const XE* __restrict__ x, int64_t nchunks, double never,
                                                   double* __restrict__ sink) {
@@ -670,9 +700,33 @@ __global__ __launch_bounds__(256) void stream_chunk_kernel_f32(const float* __re
     stream_chunk_body(x, nchunks, never, sink);
 }
 
-hipError_t stream_read(const void* x, int f32, int64_t n, int kind, int cus, hipStream_t st, const Timing& tm,
+// (16-byte loads, 1 MiB per wave: see stream_lock_kernel_u16)
+__global__ __launch_bounds__(256) void stream_chunk_kernel_u16(const uint16_t* __restrict__ x, int64_t nchunks,
+                                                               double never, double* __restrict__ sink) {
+    stream_chunk_body(reinterpret_cast<const double*>(x), nchunks, never, sink);
+}
+
+hipError_t stream_read(const void* x, int ek, int64_t n, int kind, int cus, hipStream_t st, const Timing& tm,
                        double* sink, double* bytes) {
     const double never = __builtin_nan("");
+    if (ek == kXU16) {  // n 16-bit elements are n / 4 eight-byte words, read as the double kernels read them
+        const int64_t nw = n / 4;
+        if (kind == 0) {
+            const int64_t units = nw / 1024;
+            if (units < cus) return hipErrorInvalidValue;
+            *bytes = 8.0 * (double)(units * 1024);
+            hipExtLaunchKernelGGL(stream_lock_kernel_u16, dim3(cus), dim3(512), 0, st, tm.start, tm.stop, 0,
+                                  static_cast<const uint16_t*>(x), units, never, sink);
+        } else {
+            const int64_t nch = nw / (1 << 17);
+            if (nch < 1) return hipErrorInvalidValue;
+            *bytes = 8.0 * (double)(nch << 17);
+            hipExtLaunchKernelGGL(stream_chunk_kernel_u16, dim3((unsigned)((nch + 3) / 4)), dim3(256), 0, st,
+                                  tm.start, tm.stop, 0, static_cast<const uint16_t*>(x), nch, never, sink);
+        }
+        return hipGetLastError();
+    }
+    const bool f32 = ek == kXF32;
     const double esize = f32 ? 4.0 : 8.0;
     if (kind == 0) {
         const int64_t units = n / 1024;
@@ -721,7 +775,7 @@ hipError_t vec_div(int K, int64_t n, int64_t /*ld*/, Ptrs v, double div, hipStre
 // per loop trip.  Every u value loaded serves G markers.  The wave's partial
 // dots are reduced with an xor butterfly; mode 1 fuses the lmmse_mult
 // epilogue (src/vamp.cpp:656-659).
-// (the body of atx_kernel and atx_kernel_f32: XE is X's element type)
+// (the body of atx_kernel, atx_kernel_f32 and atx_kernel_u16: XE is X's element type)
 template <int G, int K, int MODE, int UJ, bool NT, class XE>
 __device__ __forceinline__ void atx_body(const XE* __restrict__ X, int64_t ld, int64_t N, int64_t M,
                                          const double* __restrict__ mave, const double* __restrict__ msig,
@@ -825,6 +879,16 @@ __global__ __launch_bounds__(kBlock) void atx_kernel_f32(const float* __restrict
     atx_body<G, K, MODE, UJ, NT>(X, ld, N, M, mave, msig, u, out, scale, tau, gam2, pv, gate, zf, beta, sraw);
 }
 
+template <int G, int K, int MODE, int UJ, bool NT>
+__global__ __launch_bounds__(kBlock) void atx_kernel_u16(const uint16_t* __restrict__ X, int64_t ld, int64_t N,
+                                                         int64_t M, const double* __restrict__ mave,
+                                                         const double* __restrict__ msig, CPtrs u, Ptrs out,
+                                                         double scale, double tau, double gam2, CPtrs pv,
+                                                         const int* __restrict__ gate, CPtrs zf,
+                                                         const double* __restrict__ beta, Ptrs sraw) {
+    atx_body<G, K, MODE, UJ, NT>(X, ld, N, M, mave, msig, u, out, scale, tau, gam2, pv, gate, zf, beta, sraw);
+}
+
 // tuning table (markers per wave G, 128-row steps per trip UJ, nontemporal)
 struct AtxVariant { int G, UJ; bool NT; };
 static constexpr AtxVariant kAtxVariants[] = {
@@ -839,9 +903,9 @@ int atx_variant_count() { return kNumAtxVariants; }
 bool atx_variant_ok(int v) { return v >= -1 && v < kNumAtxVariants; }
 
 // rocprofv3 kernel name of the launch that ax_partial / atx would make now
-std::string kernel_name(int which, int K, int mode, int variant, int f32) {
+std::string kernel_name(int which, int K, int mode, int variant, int ek) {
     char b[160];
-    const char* sfx = f32 ? "_f32" : "";
+    const char* sfx = xe_suffix(ek);
     if (which == 0) {
         const AxVariant& v = kAxVariants[variant >= 0 && variant < kNumAxVariants ? variant : 0];
         std::snprintf(b, sizeof b, "ax_partial_kernel%s<%d, %d, %d, %s, %s>", sfx, K, v.R, v.U,
@@ -862,7 +926,11 @@ static void launch_atx(const Shard& s, CPtrs u, Ptrs out, double scale, double t
     // two waves per workgroup: a finer dispatch grain than four (C2: -2..4%,
     // profiles/r01_kbench_ax_swap.txt); VAMPOMI_ATX_WPB: tuning experiments
     static const int wpb = std::getenv("VAMPOMI_ATX_WPB") ? std::max(1, std::min(4, std::atoi(std::getenv("VAMPOMI_ATX_WPB")))) : 2;
-    if (s.f32)
+    if (s.u16)
+        hipExtLaunchKernelGGL((atx_kernel_u16<G, K, MODE, UJ, NT>), dim3((unsigned)cdiv(s.M, wpb * G)),
+                              dim3(64 * wpb), 0, st, tm.start, tm.stop, 0, s.x16(), s.ld, s.N, s.M, s.mave, s.msig, u,
+                              out, scale, tau, gam2, p, gate, zf, beta, sraw);
+    else if (s.f32)
         hipExtLaunchKernelGGL((atx_kernel_f32<G, K, MODE, UJ, NT>), dim3((unsigned)cdiv(s.M, wpb * G)),
                               dim3(64 * wpb), 0, st, tm.start, tm.stop, 0, s.x32(), s.ld, s.N, s.M, s.mave, s.msig, u,
                               out, scale, tau, gam2, p, gate, zf, beta, sraw);
@@ -1013,7 +1081,7 @@ struct OpCol {
     double mu;
 };
 
-// (the body of atax_kernel and atax_kernel_f32: XE is X's element type)
+// (the body of atax_kernel, atax_kernel_f32 and atax_kernel_u16: XE is X's element type)
 template <int K, int S, class XE>
 __device__ __forceinline__ void atax_body(const XE* __restrict__ X, int64_t ld, int64_t N, int64_t M,
                                           const double* __restrict__ mave, const double* __restrict__ msig,
@@ -1212,10 +1280,18 @@ __global__ __launch_bounds__(kOpThreads) void atax_kernel_f32(const float* __res
     atax_body<K, S>(X, ld, N, M, mave, msig, a, gate);
 }
 
-std::string op_kernel_name(int K, const OpPlan& pl, int f32) {
-    if (pl.T > 0) return team_kernel_name(K, pl, f32);
+template <int K, int S>
+__global__ __launch_bounds__(kOpThreads) void atax_kernel_u16(const uint16_t* __restrict__ X, int64_t ld, int64_t N,
+                                                              int64_t M, const double* __restrict__ mave,
+                                                              const double* __restrict__ msig, OpArgs a,
+                                                              const int* __restrict__ gate) {
+    atax_body<K, S>(X, ld, N, M, mave, msig, a, gate);
+}
+
+std::string op_kernel_name(int K, const OpPlan& pl, int ek) {
+    if (pl.T > 0) return team_kernel_name(K, pl, ek);
     char b[96];
-    std::snprintf(b, sizeof b, "atax_kernel%s<%d, %d>", f32 ? "_f32" : "", K, pl.S);
+    std::snprintf(b, sizeof b, "atax_kernel%s<%d, %d>", xe_suffix(ek), K, pl.S);
     return b;
 }
 
@@ -1243,6 +1319,15 @@ static hipError_t launch_op(const Shard& s, const OpPlan& pl, const OpArgs& a, h
                             const int* gate) {
     const size_t lds = ((size_t)K * (s.N + 1 + (s.N & 1)) + 2 + 2 * kOpWaves * K) * sizeof(double);
     static std::atomic<unsigned long long> allowed{0};  // more than 64 KiB of dynamic LDS must be allowed explicitly
+    if (s.u16) {
+        static std::atomic<unsigned long long> allowed16{0};
+        if (const hipError_t e =
+                lds_allow(reinterpret_cast<const void*>(&atax_kernel_u16<K, S>), allowed16, 160 * 1024))
+            return e;
+        hipExtLaunchKernelGGL((atax_kernel_u16<K, S>), dim3(pl.grid), dim3(kOpThreads), lds, st, tm.start, tm.stop, 0,
+                              s.x16(), s.ld, s.N, s.M, s.mave, s.msig, a, gate);
+        return hipSuccess;
+    }
     if (s.f32) {
         static std::atomic<unsigned long long> allowed32{0};
         if (const hipError_t e =
@@ -1367,7 +1452,7 @@ hipError_t op_reduce(const OpPlan& pl, int K, int64_t N, int64_t ld, const doubl
 // ---------------------------------------------------------------------------
 // marker statistics (src/data.cpp:233-283): one wave per marker, two passes
 // ---------------------------------------------------------------------------
-// (the body of stats_kernel and stats_kernel_f32: the statistics of the stored
+// (the body of stats_kernel, stats_kernel_f32 and stats_kernel_u16: the statistics of the stored
 // values, widened, summed in fp64)
 template <class XE>
 __device__ __forceinline__ void stats_body(const XE* __restrict__ X, int64_t ld, int64_t N, int64_t M, double nonas,
@@ -1423,10 +1508,19 @@ __global__ __launch_bounds__(kBlock) void stats_kernel_f32(const float* __restri
     stats_body(X, ld, N, M, nonas, alpha_scale, mave, msig);
 }
 
+__global__ __launch_bounds__(kBlock) void stats_kernel_u16(const uint16_t* __restrict__ X, int64_t ld, int64_t N,
+                                                           int64_t M, double nonas, double alpha_scale,
+                                                           double* __restrict__ mave, double* __restrict__ msig) {
+    stats_body(X, ld, N, M, nonas, alpha_scale, mave, msig);
+}
+
 hipError_t marker_stats(const Shard& s, double nonas, double alpha_scale, double* mave, double* msig,
                         hipStream_t st) {
     if (s.M <= 0) return hipSuccess;
-    if (s.f32)
+    if (s.u16)
+        hipLaunchKernelGGL(stats_kernel_u16, dim3((unsigned)cdiv(s.M, 4)), dim3(kBlock), 0, st, s.x16(), s.ld, s.N,
+                           s.M, nonas, alpha_scale, mave, msig);
+    else if (s.f32)
         hipLaunchKernelGGL(stats_kernel_f32, dim3((unsigned)cdiv(s.M, 4)), dim3(kBlock), 0, st, s.x32(), s.ld, s.N,
                            s.M, nonas, alpha_scale, mave, msig);
     else
@@ -1460,12 +1554,13 @@ __global__ void gen_kernel_f32(uint64_t seed, int kind, int64_t N, int64_t ld, i
     gen_body(seed, kind, N, ld, S, M, X);
 }
 
-hipError_t gen_markers(uint64_t seed, int kind, int64_t N, int64_t ld, int64_t S, int64_t M, void* X, int f32,
+hipError_t gen_markers(uint64_t seed, int kind, int64_t N, int64_t ld, int64_t S, int64_t M, void* X, int ek,
                        hipStream_t st) {
     int64_t blocks = cdiv(M * ld, kBlock);
     if (blocks > 65536) blocks = 65536;
     if (blocks < 1) return hipSuccess;
-    if (f32)
+    if (ek == kXU16) return hipErrorInvalidValue;  // quantised from staged fp64 chunks by the engine
+    if (ek == kXF32)
         hipLaunchKernelGGL(gen_kernel_f32, dim3((unsigned)blocks), dim3(kBlock), 0, st, seed, kind, N, ld, S, M,
                            static_cast<float*>(X));
     else
@@ -1496,6 +1591,115 @@ __global__ __launch_bounds__(kBlock) void widen_kernel(const float* __restrict__
         const int64_t c = e / N, j = e - c * N;
         dst[c * ldd + j] = (double)src[c * lds + j];
     }
+}
+
+// ---------------------------------------------------------------------------
+// 16-bit fixed-point storage: quantisation at ingest, read-back
+// ---------------------------------------------------------------------------
+// dst = min(65535, rint(x * 65536)) for 0 <= x <= 1 (x * 65536 is exact, rint
+// rounds ties to even, -0.0 compares equal to 0); anything else (NaN fails both
+// comparisons) is rejected: stored as 0 and counted.  Each wave folds what its
+// lanes saw (integer sums, a minimum, a maximum of non-negative doubles, which
+// order as their bit patterns do) and lane 0 adds it to *rec with ordinary
+// atomics, so the record does not depend on the order anything ran in.
+template <class XS>
+__global__ __launch_bounds__(kBlock) void quantise_kernel(const XS* __restrict__ src, int64_t lds, int64_t N,
+                                                          int64_t ncols, uint16_t* __restrict__ dst, int64_t ldd,
+                                                          int64_t col0, QuantRec* __restrict__ rec) {
+    const int64_t total = N * ncols;
+    unsigned long long rejected = 0, clamped = 0, first = ~0ull;
+    double err = 0.0;
+    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += (int64_t)gridDim.x * kBlock) {
+        const int64_t c = e / N, j = e - c * N;
+        const double x = (double)src[c * lds + j];
+        unsigned k = 0;
+        if (x >= 0.0 && x <= 1.0) {
+            const double r = __builtin_rint(x * 65536.0);
+            if (r > 65535.0) {
+                k = 65535u;
+                ++clamped;
+            } else {
+                k = (unsigned)r;
+            }
+            const double d = fabs((double)k * 0x1p-16 - x);
+            err = d > err ? d : err;
+        } else {
+            ++rejected;
+            const unsigned long long at = (unsigned long long)((col0 + c) * N + j);
+            first = at < first ? at : first;
+        }
+        dst[c * ldd + j] = (uint16_t)k;
+    }
+    unsigned long long eb = (unsigned long long)__double_as_longlong(err);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        rejected += __shfl_xor(rejected, o, 64);
+        clamped += __shfl_xor(clamped, o, 64);
+        const unsigned long long f = __shfl_xor(first, o, 64), m = __shfl_xor(eb, o, 64);
+        first = f < first ? f : first;
+        eb = m > eb ? m : eb;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (rejected) {
+            atomicAdd(&rec->rejected, rejected);
+            atomicMin(&rec->first, first);
+        }
+        if (clamped) atomicAdd(&rec->clamped, clamped);
+        if (eb) atomicMax(&rec->max_err, eb);
+    }
+}
+
+template <class XS>
+static hipError_t quantise_cols_t(const XS* src, int64_t lds, int64_t N, int64_t ncols, uint16_t* dst, int64_t ldd,
+                                  int64_t col0, QuantRec* rec, hipStream_t st) {
+    if (N <= 0 || ncols <= 0) return hipSuccess;
+    if (lds < N || ldd < N || !rec) return hipErrorInvalidValue;
+    const int64_t blocks = std::min<int64_t>(cdiv(N * ncols, kBlock), 65536);
+    hipLaunchKernelGGL(quantise_kernel<XS>, dim3((unsigned)blocks), dim3(kBlock), 0, st, src, lds, N, ncols, dst, ldd,
+                       col0, rec);
+    return hipGetLastError();
+}
+
+hipError_t quantise_cols(const double* src, int64_t lds, int64_t N, int64_t ncols, uint16_t* dst, int64_t ldd,
+                         int64_t col0, QuantRec* rec, hipStream_t st) {
+    return quantise_cols_t(src, lds, N, ncols, dst, ldd, col0, rec, st);
+}
+
+hipError_t quantise_cols(const float* src, int64_t lds, int64_t N, int64_t ncols, uint16_t* dst, int64_t ldd,
+                         int64_t col0, QuantRec* rec, hipStream_t st) {
+    return quantise_cols_t(src, lds, N, ncols, dst, ldd, col0, rec, st);
+}
+
+// dst[c*ldd + j] = src[c*lds + j] * 2^-16: exact as a double, and as a float
+// (16 significant bits)
+template <class XD>
+__global__ __launch_bounds__(kBlock) void dequant_kernel(const uint16_t* __restrict__ src, int64_t lds, int64_t N,
+                                                         int64_t ncols, XD* __restrict__ dst, int64_t ldd) {
+    const int64_t total = N * ncols;
+    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += (int64_t)gridDim.x * kBlock) {
+        const int64_t c = e / N, j = e - c * N;
+        dst[c * ldd + j] = (XD)((double)src[c * lds + j] * 0x1p-16);
+    }
+}
+
+template <class XD>
+static hipError_t dequant_cols_t(const uint16_t* src, int64_t lds, int64_t N, int64_t ncols, XD* dst, int64_t ldd,
+                                 hipStream_t st) {
+    if (N <= 0 || ncols <= 0) return hipSuccess;
+    if (lds < N || ldd < N) return hipErrorInvalidValue;
+    const int64_t blocks = std::min<int64_t>(cdiv(N * ncols, kBlock), 65536);
+    hipLaunchKernelGGL(dequant_kernel<XD>, dim3((unsigned)blocks), dim3(kBlock), 0, st, src, lds, N, ncols, dst, ldd);
+    return hipGetLastError();
+}
+
+hipError_t dequant_cols(const uint16_t* src, int64_t lds, int64_t N, int64_t ncols, double* dst, int64_t ldd,
+                        hipStream_t st) {
+    return dequant_cols_t(src, lds, N, ncols, dst, ldd, st);
+}
+
+hipError_t dequant_cols(const uint16_t* src, int64_t lds, int64_t N, int64_t ncols, float* dst, int64_t ldd,
+                        hipStream_t st) {
+    return dequant_cols_t(src, lds, N, ncols, dst, ldd, st);
 }
 
 hipError_t narrow_cols(const double* src, int64_t lds, int64_t N, int64_t ncols, float* dst, int64_t ldd,
@@ -2871,7 +3075,7 @@ hipError_t cov_offset(int64_t N, int C, const double* Z, int64_t ld, const doubl
 // of a zero quotient can differ, which no sum can see.  Every lane adds its
 // samples in increasing order whatever G / UJ are, so all variants give
 // bitwise identical sums.
-// (the body of loo_kernel and loo_kernel_f32: XE is X's element type)
+// (the body of loo_kernel, loo_kernel_f32 and loo_kernel_u16: XE is X's element type)
 template <int G, int UJ, bool FASTDIV, class XE>
 __device__ __forceinline__ void loo_body(const XE* __restrict__ X, int64_t ld, int64_t N, int64_t M,
                                          const double* __restrict__ ymod, const double* __restrict__ x1,
@@ -2952,6 +3156,14 @@ __global__ __launch_bounds__(kBlock) void loo_kernel(const double* __restrict__ 
 
 template <int G, int UJ, bool FASTDIV>
 __global__ __launch_bounds__(kBlock) void loo_kernel_f32(const float* __restrict__ X, int64_t ld, int64_t N,
+                                                         int64_t M, const double* __restrict__ ymod,
+                                                         const double* __restrict__ x1, double sqrtN,
+                                                         double* __restrict__ stats) {
+    loo_body<G, UJ, FASTDIV>(X, ld, N, M, ymod, x1, sqrtN, stats);
+}
+
+template <int G, int UJ, bool FASTDIV>
+__global__ __launch_bounds__(kBlock) void loo_kernel_u16(const uint16_t* __restrict__ X, int64_t ld, int64_t N,
                                                          int64_t M, const double* __restrict__ ymod,
                                                          const double* __restrict__ x1, double sqrtN,
                                                          double* __restrict__ stats) {
@@ -3053,6 +3265,14 @@ __global__ __launch_bounds__(64 * W) void loo_wg_kernel_f32(const float* __restr
     loo_wg_body<G, UJ, W>(X, ld, N, M, ymod, x1, sqrtN, stats);
 }
 
+template <int G, int UJ, int W>
+__global__ __launch_bounds__(64 * W) void loo_wg_kernel_u16(const uint16_t* __restrict__ X, int64_t ld, int64_t N,
+                                                            int64_t M, const double* __restrict__ ymod,
+                                                            const double* __restrict__ x1, double sqrtN,
+                                                            double* __restrict__ stats) {
+    loo_wg_body<G, UJ, W>(X, ld, N, M, ymod, x1, sqrtN, stats);
+}
+
 struct LooVariant { int G, UJ; bool FD; int W = 0; };  // W > 0: loo_wg_kernel
 static constexpr LooVariant kLooVariants[] = {
     {4, 2, true}, {4, 2, false}, {2, 2, true}, {8, 1, true}, {4, 1, true}, {4, 4, true}, {2, 4, true}, {8, 2, true},
@@ -3067,9 +3287,9 @@ static constexpr int kNumLooVariants = sizeof(kLooVariants) / sizeof(kLooVariant
 int loo_variant_count() { return kNumLooVariants; }
 bool loo_variant_ok(int v) { return v >= 0 && v < kNumLooVariants; }
 
-std::string loo_kernel_name(int variant, int f32) {
+std::string loo_kernel_name(int variant, int ek) {
     const LooVariant& v = kLooVariants[loo_variant_ok(variant) ? variant : kLooDefault];
-    const char* sfx = f32 ? "_f32" : "";
+    const char* sfx = xe_suffix(ek);
     char b[64];
     if (v.W > 0)
         std::snprintf(b, sizeof b, "loo_wg_kernel%s<%d, %d, %d>", sfx, v.G, v.UJ, v.W);
@@ -3084,7 +3304,10 @@ static void launch_loo(const Shard& s, const double* ymod, const double* x1, dou
     // two waves per workgroup, as A^T.u (C5 shape: 7339 vs 7477 us with four);
     // VAMPOMI_LOO_WPB: tuning experiments
     static const int wpb = std::getenv("VAMPOMI_LOO_WPB") ? std::max(1, std::min(4, std::atoi(std::getenv("VAMPOMI_LOO_WPB")))) : 2;
-    if (s.f32)
+    if (s.u16)
+        hipExtLaunchKernelGGL((loo_kernel_u16<G, UJ, FD>), dim3((unsigned)cdiv(s.M, wpb * G)), dim3(64 * wpb), 0, st,
+                              tm.start, tm.stop, 0, s.x16(), s.ld, s.N, s.M, ymod, x1, sqrtN, stats);
+    else if (s.f32)
         hipExtLaunchKernelGGL((loo_kernel_f32<G, UJ, FD>), dim3((unsigned)cdiv(s.M, wpb * G)), dim3(64 * wpb), 0, st,
                               tm.start, tm.stop, 0, s.x32(), s.ld, s.N, s.M, ymod, x1, sqrtN, stats);
     else
@@ -3095,7 +3318,10 @@ static void launch_loo(const Shard& s, const double* ymod, const double* x1, dou
 template <int G, int UJ, int W>
 static void launch_loo_wg(const Shard& s, const double* ymod, const double* x1, double sqrtN, double* stats,
                           hipStream_t st, const Timing& tm) {
-    if (s.f32)
+    if (s.u16)
+        hipExtLaunchKernelGGL((loo_wg_kernel_u16<G, UJ, W>), dim3((unsigned)cdiv(s.M, G)), dim3(64 * W), 0, st,
+                              tm.start, tm.stop, 0, s.x16(), s.ld, s.N, s.M, ymod, x1, sqrtN, stats);
+    else if (s.f32)
         hipExtLaunchKernelGGL((loo_wg_kernel_f32<G, UJ, W>), dim3((unsigned)cdiv(s.M, G)), dim3(64 * W), 0, st,
                               tm.start, tm.stop, 0, s.x32(), s.ld, s.N, s.M, ymod, x1, sqrtN, stats);
     else

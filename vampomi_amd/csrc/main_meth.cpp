@@ -212,7 +212,9 @@ int main(int argc, char** argv) {
     g_ctx = ctx;
     // (without the flag the context keeps its default, VAMPOMI_STORAGE included)
     if (opt.meth_storage_set &&
-        vampomi_set_storage(ctx, opt.meth_storage == "f32" ? VAMPOMI_STORE_F32 : VAMPOMI_STORE_F64) != VAMPOMI_OK)
+        vampomi_set_storage(ctx, opt.meth_storage == "u16"   ? VAMPOMI_STORE_U16
+                                 : opt.meth_storage == "f32" ? VAMPOMI_STORE_F32
+                                                             : VAMPOMI_STORE_F64) != VAMPOMI_OK)
         return die("methylation storage");
     // every rank has joined the communicator (its init is collective): the
     // rendezvous file has served and must not be read by a later job
@@ -226,8 +228,9 @@ int main(int argc, char** argv) {
     const std::string& meth = test_mode ? opt.meth_file_test : opt.meth_file;
     if (vampomi_read_phen(ctx, phen.c_str(), standardize) != VAMPOMI_OK) return die("phenotype");
     if (rank == 0) std::cout << "meth file name = " << meth << std::endl;
-    if ((opt.meth_dtype == "f32" ? vampomi_load_meth_file_f32(ctx, meth.c_str())
-                                 : vampomi_load_meth_file(ctx, meth.c_str())) != VAMPOMI_OK)
+    if ((opt.meth_dtype == "u16"   ? vampomi_load_meth_file_u16(ctx, meth.c_str())
+         : opt.meth_dtype == "f32" ? vampomi_load_meth_file_f32(ctx, meth.c_str())
+                                   : vampomi_load_meth_file(ctx, meth.c_str())) != VAMPOMI_OK)
         return die("methylation data");
     // the ranks' shards load at their own pace (one rank's file may come off
     // slower storage): they meet here under a limit of their own, so the

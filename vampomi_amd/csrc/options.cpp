@@ -90,8 +90,8 @@ bool parse(int argc, char** argv, Options& o, std::string& echo) {
         switch (fl.kind) {
             case Kind::Str:
                 if ((name == "--meth-storage" || name == "--meth-dtype") && std::strcmp(val, "f64") != 0 &&
-                    std::strcmp(val, "f32") != 0) {
-                    std::cout << "FATAL  : option " << name << " has to be f64 or f32! (" << val << " was passed)"
+                    std::strcmp(val, "f32") != 0 && std::strcmp(val, "u16") != 0) {
+                    std::cout << "FATAL  : option " << name << " has to be f64, f32 or u16! (" << val << " was passed)"
                               << std::endl;
                     return false;
                 }

@@ -26,7 +26,8 @@ struct Options {
     unsigned long long seed = 0x5EED5EEDULL;
     int batch_rhs = 4;
     // how the methylation shard is held on the device (--meth-storage) and the
-    // element type of --meth-file / --meth-file-test (--meth-dtype): f64 | f32
+    // element type of --meth-file / --meth-file-test (--meth-dtype): f64 | f32 | u16
+    // (u16: 16-bit fixed point, k * 2^-16)
     std::string meth_storage = "f64", meth_dtype = "f64";
     bool meth_storage_set = false;  // --meth-storage was given (else the context's default stands)
 };
