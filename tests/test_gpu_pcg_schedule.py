@@ -85,12 +85,32 @@ def _run_vamp(d, case):
         d.set_variant(which, value)
     d.set_phen(y, standardize=False)
     v = va.Vamp(d, va.VampOptions(model=case["model"], **case["opts"]), true_signal=beta[d.S:d.S + d.M])
-    v.infere(keep_hist=True)
+    if case.get("step_after_stop"):
+        _run_stepwise(d, v)
+    else:
+        v.infere(keep_hist=True)
     s = v.summary()
     n = s["iterations"]
     out = _stats(d)
     out.update(cg_iters=s["cg_iters"], ons_iters=s["ons_iters"], prestep_counts=list(d.prestep_counts()))
+    if case.get("tail"):  # what the iteration's tail forms (tests/test_gpu_vamp_schedule.py)
+        out.update(iterations=n, L=s["L"], params=_sha(s["params"]), metrics=_sha(s["metrics"]))
     return out, v.x1_hist[:n, :d.M].copy(), v.r1_hist[:n, :d.M].copy()
+
+
+def _run_stepwise(d, v):
+    """The run through the step-wise API; once it has stopped, one more step
+    reports stopped and queues, waits for and counts nothing."""
+    def counters():
+        return dict(_stats(d), iterations=v.iterations_run, a_passes=v.a_passes, prestep=d.prestep_counts())
+
+    v.begin(keep_hist=True)
+    while not v.step():
+        pass
+    before = counters()
+    assert v.step() is True
+    assert counters() == before
+    v.end()
 
 
 def _run_pcg(d, case):
@@ -107,11 +127,14 @@ def _run_pcg(d, case):
     return out
 
 
-def run_case(name, monkeypatch):
-    """What the fixture holds for one case, from one run."""
-    case = CASES[name]
+def run_case(name, monkeypatch, cases=None):
+    """What the fixture holds for one case (of CASES, or of cases), from one run."""
+    case = (CASES if cases is None else cases)[name]
     for k, val in case.get("env", {}).items():
-        monkeypatch.setenv(k, val)
+        if val is None:
+            monkeypatch.delenv(k, raising=False)
+        else:
+            monkeypatch.setenv(k, val)
     if case["run"] == "pcg":
         with va.Data(case["N"], case["Mt"]) as d:
             return _run_pcg(d, case)

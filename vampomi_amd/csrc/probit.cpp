@@ -302,23 +302,14 @@ vampomi_status probit_step(vampomi_ctx* c, VampRun& R) {
         std::printf("it %d: alpha1 %.6g beta1 %.6g gam1 %.6g tau1 %.6g alpha2 %.6g beta2 %.6g L %d cg %d/%d\n", it,
                     R.alpha1, R.beta1, R.gam1, R.tau1, R.alpha2, R.beta2, R.mix.L, sx.iters, so.iters);
 
-    // stopping criteria (:444-458)
-    const double NMSE = std::sqrt(R.nm[0] / R.nm[1]);
-    if ((it > 1 && NMSE < R.prm.stop_criteria_thr) || it >= R.prm.max_iter) R.stopped = true;
-    STCHK(end_iteration_io(c, R));  // write_bins' and the rows' failures, on every rank at once
-    R.have_next = next && !R.stopped;
+    // stopping criteria (:444-458) and the bookkeeping shared with the linear model
+    STCHK(finish_iteration(c, R, it, next));
     if (R.have_next) {  // (after this iteration's prior row: the update is iteration it+1's)
         if (em_h_on) {
             STCHK(em_finish(c, em_params(R), R.mix, R.gam1, R.r1, em_h));
             R.em_head = it + 1;
         }
         R.z_head = it + 1;
-    }
-    if (R.have_next) R.alpha1_next = R.sum_d / (double)Mt;
-    if (res) {
-        res->iterations_run = it;
-        res->a_passes_ref = R.passes_ref;
-        res->a_passes_exec = c->stats.a_passes_exec;
     }
     return VAMPOMI_OK;
 }

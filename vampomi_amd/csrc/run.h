@@ -158,6 +158,11 @@ vampomi_status agree_io(vampomi_ctx* c, VampRun& R, bool wait_all = false);
 // row is in place, and write failures so far (all writes after the last
 // iteration) are agreed over the ranks.  COLLECTIVE when writing files
 vampomi_status end_iteration_io(vampomi_ctx* c, VampRun& R);
+// the end of iteration it of either model, after its rows are queued: the
+// stopping rule on R.nm, end_iteration_io, R.have_next (next: the iteration
+// prefetched it + 1's start, kept unless the run stops) with alpha1_next, and
+// the result's counters.  COLLECTIVE when writing files
+vampomi_status finish_iteration(vampomi_ctx* c, VampRun& R, int it, bool next);
 // probit.cpp
 vampomi_status probit_begin(vampomi_ctx* c, VampRun& R);
 vampomi_status probit_step(vampomi_ctx* c, VampRun& R);

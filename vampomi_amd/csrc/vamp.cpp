@@ -36,6 +36,15 @@
 // (pcg_run's PreMode::ahead).  The host waits once, at the end, forms the
 // same scalars and mixture from the same sums, and checks the device's bit
 // for bit after the next solves (check_device_values).
+//
+// vampomi_vamp_step is a driver.  linear_step runs the iteration's phases:
+// denoise_head; lmmse_setup and lmmse_solves (pcg_run in its head-start,
+// shared-pass or one-after-the-other form, PcgArgs from pcg_args); tail_plan,
+// which decides once what the tail does (TailPlan); the tail of that kind:
+// tail_chained (the host-free tail above; several ranks: mr_post),
+// tail_host_arec (batch_rhs >= 3, the host waiting for alpha2) or
+// tail_passes (batch_rhs <= 2, updateNoisePrec's own pass over X); and
+// close_linear, ending in finish_iteration, which the probit step shares.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -451,7 +460,9 @@ static vampomi_status check_device_mix(VampRun& R) {
 // The LMMSE half's solves of iteration it (src/vamp.cpp:289-350): their
 // vectors, schedule flags and the prelude (r2, the probe bern, v and the zero
 // starts, :259-261, :295-306, :496), from R's scalars and x1 (iteration it's
-// x1_hat).  No launches: vamp_step queues them, and the previous iteration
+// x1_hat).  prefetched: iteration it starts from what it - 1 prefetched
+// (R.have_next as it will see it), so atx0 holds its warm start's product.
+// No launches: lmmse_solves queues them, and the previous iteration's tail
 // may queue the prelude and the solves' start ahead (R.pre_ahead).
 struct LmmseSetup {
     CgSystem sx{}, so{};
@@ -460,14 +471,15 @@ struct LmmseSetup {
     vk::Prelude pr{};
 };
 
-static vampomi_status lmmse_setup(vampomi_ctx* c, VampRun& R, int it, const double* x1, LmmseSetup& L) {
+static vampomi_status lmmse_setup(vampomi_ctx* c, VampRun& R, int it, const double* x1, bool prefetched,
+                                  LmmseSetup& L) {
     const int64_t ld = c->ld;
     CgSystem& sx = L.sx;
     CgSystem& so = L.so;
     sx.v = R.v;
     sx.mu = R.x2;  // mu_CG_last: warm start, updated in place (:308-311, :753-754)
     sx.mu0_nonzero = it > 1;
-    sx.atx0 = (it > 1 && R.have_next) ? R.atx0 : nullptr;
+    sx.atx0 = (it > 1 && prefetched) ? R.atx0 : nullptr;
     sx.r = R.cgw[0];
     sx.z = R.cgw[1];
     sx.p = R.cgw[2];
@@ -555,30 +567,16 @@ static vampomi_status check_device_values(vampomi_ctx* c, VampRun& R, int it) {
     return VAMPOMI_OK;
 }
 
-// one VAMP iteration (src/vamp.cpp:148-428)
-extern "C" vampomi_status vampomi_vamp_step(vampomi_ctx* c, int* stopped) {
-    CollScope cs_(c);
-    if (!c || !c->run) return fail(VAMPOMI_ERR_STATE, "vampomi_vamp_begin not called");
-    VampRun& R = *c->run;
-    if (R.stopped || R.it >= R.prm.max_iter) {
-        R.stopped = true;
-        if (stopped) *stopped = 1;
-        return VAMPOMI_OK;
-    }
-    HIPCHK(hipSetDevice(c->device));
-    const auto t_step = std::chrono::steady_clock::now();
-    if (R.probit) {
-        STCHK(probit_step(c, R));
-        R.ph_step_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_step).count();
-        if (c->timing) resolve_timing(c);
-        if (stopped) *stopped = R.stopped ? 1 : 0;
-        return VAMPOMI_OK;
-    }
-    const int64_t M = c->M, N = c->N, Mt = c->Mt, ld = c->ld;
-    const int it = ++R.it;
-    vampomi_result* res = R.res;
+// ---- the phases of one linear VAMP iteration (src/vamp.cpp:148-428), in the
+// order linear_step runs them ----
 
-    // ---------------- denoising (:177-232) ----------------
+// The head, denoising (:177-256): this iteration's x1_hat, fresh or
+// prefetched by the previous iteration's tail, then eta1, gam2 and the x1 / r1
+// output; err_measures of x1 (:272) is queued into e1 where the solves' start
+// flushes it (the forms without arec)
+static vampomi_status denoise_head(vampomi_ctx* c, VampRun& R, int it, DotBatch& e1) {
+    const int64_t Mt = c->Mt, ld = c->ld;
+    vampomi_result* res = R.res;
     if (!R.have_next) {
         if (it > R.prm.learn_prior_delay) STCHK(update_prior(c, R, R.mix, R.gam1, R.r1));  // :186-187
         std::swap(R.x1, R.x1p);  // x1_hat_prev = x1_hat (:203)
@@ -605,66 +603,77 @@ extern "C" vampomi_status vampomi_vamp_step(vampomi_ctx* c, int* stopped) {
     R.eta1 = R.gam1 / R.alpha1;  // :230
     STCHK(write_bins(c, R));     // :235-249
     R.gam2 = smin(smax(R.eta1 - R.gam1, 1e-11), 1e11);  // :255-256
-    DotBatch e1(c);
     if (!R.arec) STCHK(err_queue(c, R, R.x1, R.z1, e1, R.e1m, R.e1n, R.e1s));  // :272, flushed with the CG start
     R.params[0] = R.alpha1;
     R.params[1] = R.gam1;
+    return VAMPOMI_OK;
+}
 
-    // ---------------- LMMSE (:289-350) ----------------
-    // (r2 (:259-261), the probe bern (:295-296, P2) and v = gamw ATx(y) + gam2 r2
-    // (:303-306) are formed by the prelude launch below, with the zero starts)
-    R.passes_ref += 1;
-    LmmseSetup L;
-    STCHK(lmmse_setup(c, R, it, R.x1, L));
+// pcg_run's arguments for the solves L describes, of this iteration (pm
+// normal or queued) or of the next, queued ahead (pm ahead), whose x1_hat is
+// x1.  The forms that start on the device (arec) carry z1 = A x1 and the
+// prelude in the solve's first launches; the others flush a caller's batch
+// with the start (PcgArgs::init, set by the caller)
+static PcgArgs pcg_args(VampRun& R, LmmseSetup& L, const double* x1, PreMode pm) {
+    PcgArgs a;
+    if (pm != PreMode::ahead) {  // (ahead: tau and gam2 come from the device, the passes are counted when it runs)
+        a.tau = R.gamw;
+        a.gam2 = R.gam2;
+        a.ref_passes = &R.passes_ref;
+    }
+    a.max_iter = R.prm.CG_max_iter;
+    a.tol = R.prm.CG_err_tol;
+    a.nscratch = R.nsc;
+    a.onepass = R.onepass;
+    if (L.arec) {
+        a.extra_x = x1;
+        a.ex_out = R.z1buf;
+        a.pre = &L.pr;
+    }
+    if (L.hs_av) {
+        a.hs = &L.hs;
+        a.pm = pm;
+    }
+    return a;
+}
+
+// The solves, LMMSE (:289-350): the first iteration's zero starts, the prelude
+// (its own launch, or inside the solve's start), the x2 and the Onsager solve
+// in one of three forms, and the check of what the device formed ahead.
+// (r2 (:259-261), the probe bern (:295-296, P2) and v = gamw ATx(y) + gam2 r2
+// (:303-306) are formed by the prelude launch, with the zero starts)
+static vampomi_status lmmse_solves(vampomi_ctx* c, VampRun& R, int it, LmmseSetup& L, DotBatch& e1) {
+    const int64_t M = c->M, ld = c->ld;
+    vampomi_result* res = R.res;
     CgSystem& sx = L.sx;
     CgSystem& so = L.so;
-    const bool rec = L.rec, arec = L.arec, hs_av = L.hs_av;
     HeadStart& hs = L.hs;
-    vk::Prelude& pr = L.pr;
+    R.passes_ref += 1;
     if (it == 1) {  // the zero starts of the first iteration
         HIPCHK(hipMemsetAsync(R.x2, 0, (size_t)std::max<int64_t>(M, 1) * 8, c->st));
-        if (rec) HIPCHK(hipMemsetAsync(R.atx0, 0, (size_t)std::max<int64_t>(M, 1) * 8, c->st));
-        if (arec) HIPCHK(hipMemsetAsync(R.ax2, 0, (size_t)ld * 8, c->st));
+        if (L.rec) HIPCHK(hipMemsetAsync(R.atx0, 0, (size_t)std::max<int64_t>(M, 1) * 8, c->st));
+        if (L.arec) HIPCHK(hipMemsetAsync(R.ax2, 0, (size_t)ld * 8, c->st));
     }
     // the prelude and the solves' start of this iteration queued by the
     // previous one (its scalars from the device, R.pre_ahead)
     const PreMode pm = R.pre_ahead == it ? PreMode::queued : PreMode::normal;
-    if (pm == PreMode::queued && !(L.pre_in_cg && R.fuse && hs_av))
+    if (pm == PreMode::queued && !(L.pre_in_cg && R.fuse && L.hs_av))
         return fail(VAMPOMI_ERR_STATE, "vamp: the start queued ahead does not match this iteration's schedule");
-    if (!L.pre_in_cg) HIPCHK(vk::prelude(M, pr, c->st));
+    if (!L.pre_in_cg) HIPCHK(vk::prelude(M, L.pr, c->st));
     const auto t_solve = std::chrono::steady_clock::now();
-    PcgArgs pargs;  // what this iteration's solves share
-    pargs.tau = R.gamw;
-    pargs.gam2 = R.gam2;
-    pargs.max_iter = R.prm.CG_max_iter;
-    pargs.tol = R.prm.CG_err_tol;
-    pargs.nscratch = R.nsc;
-    pargs.ref_passes = &R.passes_ref;
-    if (R.fuse && hs_av) {
-        pargs.extra_x = R.x1;
-        pargs.ex_out = R.z1buf;
-        pargs.onepass = true;
-        pargs.hs = &hs;
-        pargs.pre = &pr;
-        pargs.pm = pm;
+    PcgArgs pargs = pcg_args(R, L, R.x1, pm);  // what this iteration's solves share
+    if (R.fuse && L.hs_av) {  // the head start: the Onsager solve first, one step ahead
         STCHK(pcg_run(c, {&so, &sx}, pargs));
         R.hs_it = hs.xnext ? it + 1 : 0;
         // T1, U1 made by this solve are the next one's (consumed before that solve refills them)
         R.pre_it = hs.pre_made ? it + 1 : 0;
         c->pre_made_n += hs.pre_made ? 1 : 0;
         c->pre_used_n += hs.pre_used ? 1 : 0;
-    } else if (R.fuse) {
-        if (arec) {
-            pargs.extra_x = R.x1;
-            pargs.ex_out = R.z1buf;
-            pargs.pre = &pr;
-        } else {
-            pargs.init = &e1;
-        }
-        pargs.onepass = R.onepass;
+    } else if (R.fuse) {  // the two solves share each pass
+        if (!L.arec) pargs.init = &e1;
         STCHK(pcg_run(c, {&sx, &so}, pargs));
         R.hs_it = R.pre_it = 0;
-    } else {
+    } else {  // one after the other
         R.pre_it = 0;
         PcgArgs first = pargs;
         first.init = &e1;
@@ -675,11 +684,19 @@ extern "C" vampomi_status vampomi_vamp_step(vampomi_ctx* c, int* stopped) {
     STCHK(check_device_values(c, R, it));  // (the solves' flags came after the previous iteration's launches)
     if (res && res->cg_iters) res->cg_iters[it - 1] = sx.iters;
     if (res && res->ons_iters) res->ons_iters[it - 1] = so.iters;
-    // r1 (:348-350): its own launch, or (the EM round below) formed by the
-    // first EM round's kernel
-    const bool next = R.fuse && it < R.prm.max_iter;
-    const bool em_next = next && it + 1 > R.prm.learn_prior_delay;
-    const bool r1_in_em = next && arec && em_next && R.prm.EM_max_iter >= 1;
+    return VAMPOMI_OK;
+}
+
+// What the tail of iteration it does, decided once (tail_plan) from R, c and
+// the iteration's schedule; the tail's functions derive nothing themselves.
+struct TailPlan {
+    // the next iteration's denoising (and the vectors its solves start from)
+    // is prefetched: discarded if the stop fires
+    bool next = false;
+    bool em_next = false;  // ... after its updatePrior (:186-187, it + 1 > learn_prior_delay)
+    // r1 (:348-350): its own launch, or (r1_in_em) formed by the first EM
+    // round's kernel
+    bool r1_in_em = false;
     // chain: alpha2 -> eta2 -> gam1 (:341-346) are formed on the device from
     // the reduction's result (vk::G1Chain), so the EM round and the reductions
     // after it are queued without the host waiting for alpha2; the host forms
@@ -688,36 +705,108 @@ extern "C" vampomi_status vampomi_vamp_step(vampomi_ctx* c, int* stopped) {
     // one-rank launches' last blocks form is formed by a one-thread launch
     // after it (vk::tail_post), all on the main stream (DotBatch::reduce_now);
     // VAMPOMI_MR_TAIL=0: the host waits at each level instead (round 4)
-    const bool chain = r1_in_em && (!c->use_comm || c->mr_tail);
-    const bool mr = chain && c->use_comm;
-    const DotBatch::Group ga2{{T(R.bern, R.invQ)}, true, &R.a2};  // :498
+    bool chain = false, mr = false;
+    // devem (the chain, one EM round): the EM round's launch also forms the
+    // update of the mixture (vk::EmArgs.upd), and the next denoising follows
+    // with no host wait between them; the host forms the same mixture from the same
+    // sums at the iteration's one flush, and checks it against the device's,
+    // bit for bit
+    bool devem = false;
+    // ahead (devem): iteration it+1's prelude and solves' start are queued at
+    // the end of this iteration, its scalars formed by the next denoising's
+    // launch (vk::PreOut): the GPU runs it while the host waits for this
+    // iteration's flush, instead of idling from the end of this iteration's
+    // last launch to the host's first launch of the next.  If the stop fires,
+    // it has only written vectors that no later read depends on (r2, v, bern,
+    // the CG start, the zero starts)
+    bool ahead = false;
+    LmmseSetup A;   // ahead: iteration it+1's solves
+    vk::PreOut po;  // ahead: where the next denoising's launch forms their scalars
+};
+
+static vampomi_status tail_plan(vampomi_ctx* c, VampRun& R, int it, const LmmseSetup& L, TailPlan& t) {
+    t.next = R.fuse && it < R.prm.max_iter;
+    t.em_next = t.next && it + 1 > R.prm.learn_prior_delay;
+    t.r1_in_em = t.next && L.arec && t.em_next && R.prm.EM_max_iter >= 1;
+    t.chain = t.r1_in_em && (!c->use_comm || c->mr_tail);
+    t.mr = t.chain && c->use_comm;
+    t.devem = t.chain && R.prm.EM_max_iter == 1;
+    if (t.devem && R.pre_ahead_on) {  // (devem: next holds)
+        double* dsc = c->scal + SL_CHAIN;
+        STCHK(lmmse_setup(c, R, it + 1, R.x1n, true, t.A));  // (it + 1's view: its x1_hat is x1n)
+        t.po.tn = dsc + 8;  // (device copies of the chained tail's sums)
+        t.po.tc = dsc + 9;
+        t.po.Mt = (double)c->Mt;
+        t.po.N = (double)c->N;
+        t.po.out = dsc + 3;
+        t.po.mirror = R.mixh_dev + vk::kMixWords;
+        t.ahead = t.A.pre_in_cg && R.fuse && t.A.hs_av && t.A.sx.atx0 && t.po.tn && t.po.tc;
+        t.A.pr.dev.scal = t.po.out;
+    }
+    return VAMPOMI_OK;
+}
+
+// ---- what the tail's kinds share ----
+
+// alpha2, eta2 and gam1 (:341-346, :498) and err_measures of x1 (:272) on the
+// host, from the sums a flush has brought (a2, e1*)
+static void host_gam1(VampRun& R, double gam1_prev) {
+    R.alpha2 = R.gam2 * R.a2;  // :498
+    err_finish(R, R.e1m, R.e1n, R.e1s, 1);
+    R.eta2 = R.gam2 / R.alpha2;  // :341
+    R.gam1 = smin(smax(R.eta2 - R.gam2, 1e-11), 1e11);
+    R.gam1 = R.prm.rho * R.gam1 + (1 - R.prm.rho) * gam1_prev;  // :346
+}
+
+static DotBatch::Group alpha2_group(VampRun& R) { return {{T(R.bern, R.invQ)}, true, &R.a2}; }  // :498
+// updateNoisePrec's two sums (:508-521) and the NMSE sums (:409-413); with
+// arec they ride in err_measures' launches (one per vector length)
+static DotBatch::Group trace_group(VampRun& R) { return {{T(R.bern, R.tmpM)}, true, &R.tc}; }  // <u, A^T A invQ>
+static DotBatch::Group resid_group(vampomi_ctx* c, VampRun& R) {
+    return {{T(R.ax2, c->y, vk::DIFF2)}, false, &R.tn};  // l2_norm2(temp, 0), temp = A x2 - y
+}
+static DotBatch::Group nmse_group(VampRun& R) {
+    return {{T(R.x1p, R.x1, vk::DIFF2), T(R.x1p, R.x1p)}, true, R.nm};
+}
+
+// the prefetch: denoising of iteration it+1 into x1n, the sum of its x1d
+// queued in fin (mixw, gam1dev, po: from the device, denoise_into)
+static vampomi_status denoise_next(vampomi_ctx* c, VampRun& R, DotBatch& fin, const double* mixw = nullptr,
+                                   const double* gam1dev = nullptr, const vk::PreOut* po = nullptr) {
+    return denoise_into(c, R.mix_next, R.gam1, R.r1, R.x1n, R.x1, true, R.prm.rho, R.x1d, fin, &R.sum_d, mixw,
+                        gam1dev, po);
+}
+
+// Several ranks (mr): the values that fin's synced sums give once they are
+// all-reduced, formed by one thread on the main stream (vk::TailPost)
+static vampomi_status mr_post(vampomi_ctx* c, DotBatch& fin, vk::TailPost& t, int mode, const double* sum) {
+    STCHK(fin.reduce_now());
+    t.mode = mode;
+    t.src = fin.dev_slot(sum);
+    HIPCHK(vk::tail_post(t, c->st));
+    return VAMPOMI_OK;
+}
+
+// ---- the tail, one function per kind ----
+
+// The device-chained tail (chain): no host wait before the last flush with
+// one EM round (devem), one more (the host's mixture update) with several
+static vampomi_status tail_chained(vampomi_ctx* c, VampRun& R, int it, TailPlan& t) {
+    const int64_t M = c->M, N = c->N;
     const double gam1_prev = R.gam1;
-    auto host_gam1 = [&] {
-        R.alpha2 = R.gam2 * R.a2;  // :498
-        err_finish(R, R.e1m, R.e1n, R.e1s, 1);
-        R.eta2 = R.gam2 / R.alpha2;  // :341
-        R.gam1 = smin(smax(R.eta2 - R.gam2, 1e-11), 1e11);
-        R.gam1 = R.prm.rho * R.gam1 + (1 - R.prm.rho) * gam1_prev;  // :346
-    };
-    // ---- prefetch: denoising of iteration it+1 (discarded if the stop fires) ----
     DotBatch fin(c);
     double* dsc = c->scal + SL_CHAIN;
-    // updateNoisePrec's two sums (:508-521) and the NMSE sums (:409-413); with
-    // arec they ride in err_measures' launches (one per vector length)
-    const DotBatch::Group gtc{{T(R.bern, R.tmpM)}, true, &R.tc};  // <u, A^T A invQ>
-    const DotBatch::Group gtn{{T(R.ax2, c->y, vk::DIFF2)}, false, &R.tn};  // l2_norm2(temp, 0), temp = A x2 - y
-    const DotBatch::Group gnm{{T(R.x1p, R.x1, vk::DIFF2), T(R.x1p, R.x1p)}, true, R.nm};
-    if (chain) {
+    {
         // every reduction of the iteration's tail reads vectors the solves have
         // just finished: err_measures of x1 (:272) and of x2 (:365, A x2 from
         // the CG) with the sums above: 10 terms over M and 11 over N, in ONE
         // launch (vk::dots2); each term's sum is the same fixed-order reduction
         // as in its own launch (the geometry depends on the length only)
-        std::vector<DotBatch::Group> gm{ga2}, gn;
+        std::vector<DotBatch::Group> gm{alpha2_group(R)}, gn;
         err_groups(c, R, R.x1, R.z1, R.e1m, R.e1n, R.e1s, gm, gn);
-        gm.push_back(gtc);
-        gm.push_back(gnm);
-        gn.push_back(gtn);
+        gm.push_back(trace_group(R));
+        gm.push_back(nmse_group(R));
+        gn.push_back(resid_group(c, R));
         err_groups(c, R, R.x2, R.ax2, R.e2m, R.e2n, R.e2s, gm, gn);
         // alpha2 -> eta2 -> gam1 in the M launch's last block (vk::G1Chain)
         vk::G1Chain g1;
@@ -726,114 +815,140 @@ extern "C" vampomi_status vampomi_vamp_step(vampomi_ctx* c, int* stopped) {
         g1.gam1_prev = gam1_prev;
         g1.out = dsc;
         // (tc and tn also into device memory, for the next prelude's scalars: vk::PreOut)
-        if (!mr) {
+        if (!t.mr) {
             STCHK(fin.add_pair(M, gm, &g1, &R.a2, {{&R.tc, dsc + 9}}, N, gn, {{&R.tn, dsc + 8}}));  // one launch
         } else {
             STCHK(fin.add_pair(M, gm, nullptr, nullptr, {}, N, gn, {}));
-            STCHK(fin.reduce_now());
-            vk::TailPost t;
-            t.mode = 0;
-            t.src = fin.dev_slot(&R.a2);
-            t.g1 = g1;
-            t.cp_src[0] = fin.dev_slot(&R.tc);
-            t.cp_dst[0] = dsc + 9;
-            t.cp_src[1] = fin.dev_slot(&R.tn);
-            t.cp_dst[1] = dsc + 8;
-            HIPCHK(vk::tail_post(t, c->st));
+            vk::TailPost p;
+            p.g1 = g1;
+            p.cp_src[0] = fin.dev_slot(&R.tc);
+            p.cp_dst[0] = dsc + 9;
+            p.cp_src[1] = fin.dev_slot(&R.tn);
+            p.cp_dst[1] = dsc + 8;
+            STCHK(mr_post(c, fin, p, 0, &R.a2));
         }
-    } else {
-        DotBatch b(c);
-        if (arec)
-            STCHK(err_queue(c, R, R.x1, R.z1, b, R.e1m, R.e1n, R.e1s, {ga2}));  // :272
-        else
-            STCHK(b.add_many(M, {ga2}));
-        STCHK(b.flush());
-        host_gam1();
-        if (!r1_in_em) HIPCHK(vk::lincomb_div(M, R.eta2, R.x2, R.gam2, R.r2, R.gam1, R.r1, c->st));
     }
+    // iteration it+1's EM sums, queued behind these reductions: the round's
+    // launch forms r1 itself, from the device's gam1 and eta2
     R1From r1from{R.x2, R.r2, R.eta2, R.gam2, R.gam1};
-    if (chain) r1from.dsc = dsc;
-    // devem (the chain, one EM round): the EM round's launch also forms the
-    // update of the mixture (vk::EmArgs.upd), and the next denoising follows
-    // with no host wait between them; the host forms the same mixture from the same
-    // sums at the iteration's one flush, and checks it against the device's,
-    // bit for bit
-    const bool devem = chain && R.prm.EM_max_iter == 1;
-    // ahead (devem): iteration it+1's prelude and solves' start are queued at
-    // the end of this iteration, its scalars formed by the next denoising's
-    // launch (vk::PreOut): the GPU runs it while the host waits for this
-    // iteration's flush, instead of idling from the end of this iteration's
-    // last launch to the host's first launch of the next.  If the stop fires,
-    // it has only written vectors that no later read depends on (r2, v, bern,
-    // the CG start, the zero starts)
-    LmmseSetup A;
-    vk::PreOut po;
-    bool ahead = false;
-    if (devem && R.pre_ahead_on && next) {
-        const bool had = R.have_next;
-        R.have_next = true;  // (it + 1's view: its x1_hat is x1n)
-        const vampomi_status st = lmmse_setup(c, R, it + 1, R.x1n, A);
-        R.have_next = had;
-        STCHK(st);
-        po.tn = dsc + 8;  // (device copies, above)
-        po.tc = dsc + 9;
-        po.Mt = (double)Mt;
-        po.N = (double)N;
-        po.out = dsc + 3;
-        po.mirror = R.mixh_dev + vk::kMixWords;
-        ahead = A.pre_in_cg && R.fuse && A.hs_av && A.sx.atx0 && po.tn && po.tc;
-        A.pr.dev.scal = po.out;
-    }
+    r1from.dsc = dsc;
     EmState em;
-    if (next) R.mix_next = R.mix;
-    if (next && arec) {  // iteration it+1's EM sums, queued before these reductions
-        if (em_next) {
-            vk::EmUpd eu;
-            eu.Mt = Mt;
-            eu.learn_vars = R.prm.learn_vars;
-            eu.merge_vars_thr = R.prm.merge_vars_thr;
-            eu.out = R.mixw;
-            eu.mirror = R.mixh_dev;
-            STCHK(em_begin(c, em_params(R), R.mix_next, R.gam1, R.r1, fin, em, r1_in_em ? &r1from : nullptr,
-                           devem && !mr ? &eu : nullptr));
-            if (devem && mr) {  // the round's update of the mixture, from its all-reduced sums
-                STCHK(fin.reduce_now());
-                vk::TailPost t;
-                t.mode = 1;
-                t.src = fin.dev_slot(em.sums);
-                t.L = R.mix_next.L;
-                for (int j = 0; j < R.mix_next.L; ++j) t.vars[j] = R.mix_next.vars[j];
-                t.upd = eu;
-                HIPCHK(vk::tail_post(t, c->st));
-            }
-            if (devem) {
-                STCHK(denoise_into(c, R.mix_next, R.gam1, R.r1, R.x1n, R.x1, true, R.prm.rho, R.x1d, fin, &R.sum_d,
-                                   R.mixw, dsc, ahead && !mr ? &po : nullptr));
-                if (ahead && mr) {  // the next prelude's scalars, from the all-reduced sum of x1d
-                    STCHK(fin.reduce_now());
-                    vk::TailPost t;
-                    t.mode = 2;
-                    t.src = fin.dev_slot(&R.sum_d);
-                    t.po = po;
-                    t.gam1dev = dsc;
-                    HIPCHK(vk::tail_post(t, c->st));
-                }
-            }
+    R.mix_next = R.mix;
+    vk::EmUpd eu;
+    eu.Mt = c->Mt;
+    eu.learn_vars = R.prm.learn_vars;
+    eu.merge_vars_thr = R.prm.merge_vars_thr;
+    eu.out = R.mixw;
+    eu.mirror = R.mixh_dev;
+    STCHK(em_begin(c, em_params(R), R.mix_next, R.gam1, R.r1, fin, em, &r1from, t.devem && !t.mr ? &eu : nullptr));
+    if (t.devem && t.mr) {  // the round's update of the mixture, from its all-reduced sums
+        vk::TailPost p;
+        p.L = R.mix_next.L;
+        for (int j = 0; j < R.mix_next.L; ++j) p.vars[j] = R.mix_next.vars[j];
+        p.upd = eu;
+        STCHK(mr_post(c, fin, p, 1, em.sums));
+    }
+    if (t.devem) {
+        STCHK(denoise_next(c, R, fin, R.mixw, dsc, t.ahead && !t.mr ? &t.po : nullptr));
+        if (t.ahead && t.mr) {  // the next prelude's scalars, from the all-reduced sum of x1d
+            vk::TailPost p;
+            p.po = t.po;
+            p.gam1dev = dsc;
+            STCHK(mr_post(c, fin, p, 2, &R.sum_d));
         }
     }
-    if (next && !arec) {  // the pass below carries the next z1 = A x1_hat: denoise first
-        if (em_next) STCHK(update_prior(c, R, R.mix_next, R.gam1, R.r1));
-        STCHK(denoise_into(c, R.mix_next, R.gam1, R.r1, R.x1n, R.x1, true, R.prm.rho, R.x1d, fin, &R.sum_d));
+    // updateNoisePrec (:504-529): no pass (A x2 came with the CG, the next z1
+    // comes with the next CG) and its sums were queued above, with the NMSE
+    // sums (:409-413) and err_measures of x2 (:365)
+    R.passes_ref += 3;  // :508, :518, :519
+    R.passes_ref += 1;
+    // Several EM rounds: iteration it+1's EM sums share these reductions'
+    // all-reduce and host wait; then, after the host's mixture update, its
+    // denoiser (g1, g1d, sum of g1d) goes to the last flush
+    if (!t.devem) {
+        STCHK(fin.flush());
+        host_gam1(R, gam1_prev);  // (the device formed the same values for the EM round)
+        STCHK(em_finish(c, em_params(R), R.mix_next, R.gam1, R.r1, em));
+        STCHK(denoise_next(c, R, fin));
     }
+    // iteration it+1's prelude and solves' start, queued now (set up by tail_plan)
+    if (t.ahead) {
+        STCHK(pcg_run(c, {&t.A.so, &t.A.sx}, pcg_args(R, t.A, R.x1n, PreMode::ahead)));
+        R.pre_ahead = it + 1;
+    }
+    STCHK(fin.flush());
+    if (t.devem) {
+        host_gam1(R, gam1_prev);  // (the device formed the same values)
+        STCHK(em_finish(c, em_params(R), R.mix_next, R.gam1, R.r1, em));
+        R.mix_expect = R.mix_next;  // checked after the next solves (or at the end)
+        R.mix_pending = true;
+    }
+    return VAMPOMI_OK;
+}
 
+// alpha2 (:498), alone or with err_measures of x1 (:272, arec: the forms
+// without queued it in the head), resolved by a host wait of its own; then
+// gam1 on the host and, unless the first EM round's kernel forms it, r1
+// (:348-350) by its own launch
+static vampomi_status host_gam1_r1(vampomi_ctx* c, VampRun& R, bool arec, bool r1_in_em) {
+    const double gam1_prev = R.gam1;
+    DotBatch b(c);
+    if (arec)
+        STCHK(err_queue(c, R, R.x1, R.z1, b, R.e1m, R.e1n, R.e1s, {alpha2_group(R)}));  // :272
+    else
+        STCHK(b.add_many(c->M, {alpha2_group(R)}));
+    STCHK(b.flush());
+    host_gam1(R, gam1_prev);
+    if (!r1_in_em) HIPCHK(vk::lincomb_div(c->M, R.eta2, R.x2, R.gam2, R.r2, R.gam1, R.r1, c->st));
+    return VAMPOMI_OK;
+}
+
+// The host tail on an arec schedule (batch_rhs >= 3 where the chain is not
+// on: the last iteration, before learn_prior_delay, no EM round, or several
+// ranks with VAMPOMI_MR_TAIL=0): the host waits for alpha2, then queues the
+// rest behind one more wait, or two where the next updatePrior runs
+static vampomi_status tail_host_arec(vampomi_ctx* c, VampRun& R, const TailPlan& t) {
+    STCHK(host_gam1_r1(c, R, true, t.r1_in_em));
+    DotBatch fin(c);
+    R1From r1from{R.x2, R.r2, R.eta2, R.gam2, R.gam1};
+    EmState em;
+    if (t.next) R.mix_next = R.mix;
+    if (t.em_next)  // iteration it+1's EM sums, queued before these reductions
+        STCHK(em_begin(c, em_params(R), R.mix_next, R.gam1, R.r1, fin, em, t.r1_in_em ? &r1from : nullptr));
+    // updateNoisePrec (:504-529): no pass (A x2 came with the CG, the next z1
+    // comes with the next CG); its sums and the NMSE sums (:409-413; they read
+    // x1 and x1_prev, which the prefetched denoising below does not write)
+    // ride in err_measures' launches
+    R.passes_ref += 3;  // :508, :518, :519
+    STCHK(err_queue(c, R, R.x2, R.ax2, fin, R.e2m, R.e2n, R.e2s, {trace_group(R), nmse_group(R)},
+                    {resid_group(c, R)}));  // :365 (A.x2_hat of :826)
+    R.passes_ref += 1;
+    // Iteration it+1's EM sums share these reductions' all-reduce and host
+    // wait; then its denoiser (g1, g1d, sum of g1d) shares the NMSE sums'
+    // (the host's mixture update between them)
+    if (t.em_next) {
+        STCHK(fin.flush());
+        STCHK(em_finish(c, em_params(R), R.mix_next, R.gam1, R.r1, em));
+    }
+    if (t.next) STCHK(denoise_next(c, R, fin));
+    return fin.flush();
+}
+
+// The tail with updateNoisePrec's pass over X (batch_rhs 1-2, and 0 with
+// nothing prefetched): that pass carries the next z1 = A x1_hat, so the next
+// denoising is queued first
+static vampomi_status tail_passes(vampomi_ctx* c, VampRun& R, const TailPlan& t, bool rec) {
+    const int64_t M = c->M, N = c->N, ld = c->ld;
+    const bool next = t.next;
+    STCHK(host_gam1_r1(c, R, false, false));
+    DotBatch fin(c);
+    if (next) {  // the pass below carries the next z1 = A x1_hat: denoise first
+        R.mix_next = R.mix;
+        if (t.em_next) STCHK(update_prior(c, R, R.mix_next, R.gam1, R.r1));
+        STCHK(denoise_next(c, R, fin));
+    }
     // ---- updateNoisePrec (:504-529) + the next z1 in the same pass ----
-    const double* ax2 = R.nb3;  // A.x2_hat
-    bool shared = false;
-    if (arec) {  // no pass: A x2 came with the CG, the next z1 comes with the next CG
-        ax2 = R.ax2;
-        R.passes_ref += 3;  // :508, :518, :519
-        shared = true;
-    } else if (rec) {  // A.x2 and the next z1 in one pass; the A^T products came with the CG
+    if (rec) {  // A.x2 and the next z1 in one pass; the A^T products came with the CG
         const double* xs[2] = {R.x2, R.x1n};
         STCHK(ax_dev(c, next ? 2 : 1, xs, R.nb3));
         R.z1n_slot = 1;
@@ -853,47 +968,18 @@ extern "C" vampomi_status vampomi_vamp_step(vampomi_ctx* c, int* stopped) {
         R.passes_ref += 1;
         STCHK(fin.add({T(R.bern, R.tmpM)}, M, true, &R.tc));
     }
-    // (shared: the NMSE sums (:409-413) too; they read x1 and x1_prev, which
-    // the prefetched denoising below does not write; chain: queued above)
-    if (shared && !chain)
-        STCHK(err_queue(c, R, R.x2, ax2, fin, R.e2m, R.e2n, R.e2s, {gtc, gnm}, {gtn}));  // :365 (A.x2_hat of :826)
-    else if (!shared)
-        STCHK(err_queue(c, R, R.x2, ax2, fin, R.e2m, R.e2n, R.e2s));
+    STCHK(err_queue(c, R, R.x2, R.nb3, fin, R.e2m, R.e2n, R.e2s));  // :365 (A.x2_hat of :826)
     R.passes_ref += 1;
-    // Iteration it+1's EM sums share these reductions' all-reduce and host
-    // wait; then its denoiser (g1, g1d, sum of g1d) shares the NMSE sums'
-    // (several EM rounds, or VAMPOMI_MR_TAIL=0 on several ranks: the host's
-    // mixture update between them)
-    if (next && arec && em_next && !devem) {
-        STCHK(fin.flush());
-        if (chain) host_gam1();  // (the device formed the same values for the EM round)
-        STCHK(em_finish(c, em_params(R), R.mix_next, R.gam1, R.r1, em));
-    }
-    if (next && arec && !devem)
-        STCHK(denoise_into(c, R.mix_next, R.gam1, R.r1, R.x1n, R.x1, true, R.prm.rho, R.x1d, fin, &R.sum_d));
-    if (!shared) STCHK(fin.add_many(M, {gnm}));  // NMSE (:409-413)
-    // iteration it+1's prelude and solves' start, queued now (set up above)
-    if (ahead) {
-        PcgArgs pargs;  // (tau and gam2 come from the device)
-        pargs.max_iter = R.prm.CG_max_iter;
-        pargs.tol = R.prm.CG_err_tol;
-        pargs.nscratch = R.nsc;
-        pargs.extra_x = R.x1n;
-        pargs.ex_out = R.z1buf;
-        pargs.onepass = true;
-        pargs.hs = &A.hs;
-        pargs.pre = &A.pr;
-        pargs.pm = PreMode::ahead;
-        STCHK(pcg_run(c, {&A.so, &A.sx}, pargs));
-        R.pre_ahead = it + 1;
-    }
-    STCHK(fin.flush());
-    if (devem) {
-        host_gam1();  // (the device formed the same values)
-        STCHK(em_finish(c, em_params(R), R.mix_next, R.gam1, R.r1, em));
-        R.mix_expect = R.mix_next;  // checked after the next solves (or at the end)
-        R.mix_pending = true;
-    }
+    STCHK(fin.add_many(M, {nmse_group(R)}));  // NMSE (:409-413)
+    return fin.flush();
+}
+
+// The close (:365-428): gamw from updateNoisePrec's sums, err_measures of x2,
+// the iteration's rows and lines, then the stopping rule and the bookkeeping
+// both models share (finish_iteration)
+static vampomi_status close_linear(vampomi_ctx* c, VampRun& R, int it, const LmmseSetup& L, bool next) {
+    const int64_t N = c->N, Mt = c->Mt;
+    vampomi_result* res = R.res;
     const double trace_corr = R.tc * (double)Mt;  // :521
     if (R.prm.verbosity >= 1 && c->rank == 0)
         std::printf("l2_norm2(temp) / N = %g\ntrace_correction / N = %g\n", R.tn / (double)N, trace_corr / (double)N);
@@ -910,22 +996,64 @@ extern "C" vampomi_status vampomi_vamp_step(vampomi_ctx* c, int* stopped) {
     }
     if (R.prm.verbosity >= 1 && c->rank == 0)
         std::printf("it %d: alpha1 %.6g gam1 %.6g alpha2 %.6g gam2 %.6g gamw %.6g L %d cg %d/%d\n", it, R.alpha1,
-                    R.gam1, R.alpha2, R.gam2, R.gamw, R.mix.L, sx.iters, so.iters);
+                    R.gam1, R.alpha2, R.gam2, R.gamw, R.mix.L, L.sx.iters, L.so.iters);
+    return finish_iteration(c, R, it, next);
+}
 
-    // stopping criteria (:409-423)
+// The end of an iteration of either model, once its rows are queued: the
+// stopping criteria (:409-423; src/vamp_probit.cpp:444-458), the output's end
+// (a collective when writing files), whether the prefetched start is kept,
+// and the caller's counters
+vampomi_status finish_iteration(vampomi_ctx* c, VampRun& R, int it, bool next) {
     const double NMSE = std::sqrt(R.nm[0] / R.nm[1]);
     if ((it > 1 && NMSE < R.prm.stop_criteria_thr) || it >= R.prm.max_iter) R.stopped = true;
-    STCHK(end_iteration_io(c, R));
+    STCHK(end_iteration_io(c, R));  // write_bins' and the rows' failures, on every rank at once
     R.have_next = next && !R.stopped;
-    if (R.have_next) R.alpha1_next = R.sum_d / (double)Mt;
-    if (res) {
+    if (R.have_next) R.alpha1_next = R.sum_d / (double)c->Mt;
+    if (vampomi_result* res = R.res) {
         res->iterations_run = it;
         res->a_passes_ref = R.passes_ref;
         res->a_passes_exec = c->stats.a_passes_exec;
     }
+    return VAMPOMI_OK;
+}
+
+// one linear VAMP iteration (src/vamp.cpp:148-428): the head, the solves, and
+// the tail of the kind tail_plan decides, then the close
+static vampomi_status linear_step(vampomi_ctx* c, VampRun& R) {
+    const int it = ++R.it;
+    DotBatch e1(c);
+    STCHK(denoise_head(c, R, it, e1));
+    LmmseSetup L;
+    STCHK(lmmse_setup(c, R, it, R.x1, R.have_next, L));
+    STCHK(lmmse_solves(c, R, it, L, e1));
+    TailPlan t;
+    STCHK(tail_plan(c, R, it, L, t));
+    if (t.chain)
+        STCHK(tail_chained(c, R, it, t));
+    else if (L.arec)
+        STCHK(tail_host_arec(c, R, t));
+    else
+        STCHK(tail_passes(c, R, t, L.rec));
+    return close_linear(c, R, it, L, t.next);
+}
+
+// one VAMP iteration of the run's model
+extern "C" vampomi_status vampomi_vamp_step(vampomi_ctx* c, int* stopped) {
+    CollScope cs_(c);
+    if (!c || !c->run) return fail(VAMPOMI_ERR_STATE, "vampomi_vamp_begin not called");
+    VampRun& R = *c->run;
+    if (R.stopped || R.it >= R.prm.max_iter) {
+        R.stopped = true;
+        if (stopped) *stopped = 1;
+        return VAMPOMI_OK;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    const auto t_step = std::chrono::steady_clock::now();
+    STCHK(R.probit ? probit_step(c, R) : linear_step(c, R));
+    R.ph_step_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_step).count();
     if (c->timing) resolve_timing(c);
     if (stopped) *stopped = R.stopped ? 1 : 0;
-    R.ph_step_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_step).count();
     return VAMPOMI_OK;
 }
 
