@@ -151,6 +151,49 @@ vampomi_status vampomi_comm_abort(vampomi_ctx* ctx);
  * (elements) and every kernel plan are the same for all storages. */
 vampomi_status vampomi_set_storage(vampomi_ctx* ctx, int storage);
 vampomi_status vampomi_get_storage(const vampomi_ctx* ctx, int* storage);
+/* A row subset: the files hold N_file rows (individuals) of which the context
+ * analyses the n = N listed in rows, so a phenotype's missing values, a QC list
+ * or a train/test split need no second copy of the matrix.  Open the context
+ * with N = n.  rows: strictly ascending within [0, N_file), 2 <= n <= N_file,
+ * n == the context's N, N_file < 2^31; anything else is VAMPOMI_ERR_ARG.  Legal
+ * only before the shard is allocated (as vampomi_set_storage) and before a
+ * phenotype or covariates are set: VAMPOMI_ERR_STATE afterwards.  Rank-local:
+ * every rank of a job sets the same subset.  From then on
+ *   - every vampomi_load_meth_file* reads this shard's bytes [S*N_file*es,
+ *     (S+M)*N_file*es) (es: the file's element size; a file too short for
+ *     N_file rows is VAMPOMI_ERR_IO), and vampomi_load_meth_host* takes columns
+ *     of N_file rows, ld_in >= N_file.  Every chunk is staged on the device as
+ *     it is and a gather kernel keeps the listed rows as it converts, also
+ *     where the input's element type is the storage's.  A U16 context range-checks
+ *     and counts the kept entries only, and VAMPOMI_ERR_RANGE names the
+ *     file's row;
+ *   - vampomi_read_phen and vampomi_read_covariates expect N_file rows, keep the
+ *     listed ones and only then standardise; "NA" is VAMPOMI_ERR_NAN_PHEN in a
+ *     kept row and ignored in any other.  vampomi_set_phen and
+ *     vampomi_set_covariates keep taking n rows;
+ *   - vampomi_generate_meth returns VAMPOMI_ERR_STATE.
+ * The context holds, bit for bit, what a context of N = n without a subset
+ * holds after loading files from which the other rows were removed, and so
+ * computes the same bits in everything that follows.  Without a subset every
+ * path and launch is what it is without this call. */
+vampomi_status vampomi_set_row_subset(vampomi_ctx* ctx, int64_t N_file, const int64_t* rows, int64_t n);
+/* *N_file = the subset's file rows, 0 without a subset; rows (n entries, or
+ * NULL) receives the list */
+vampomi_status vampomi_get_row_subset(const vampomi_ctx* ctx, int64_t* N_file, int64_t* rows);
+/* The rows of a PLINK phenotype file that an analysis keeps; needs no device.
+ * The file is split as vampomi_read_phen splits it: per row FID, IID and the
+ * value, missing where the value is "NA".  keep_path (or NULL): PLINK --keep
+ * style, per non-blank line FID and IID, further fields ignored; a row is kept
+ * iff its pair is named there, so the result is ascending in the phenotype
+ * file's order whatever the keep file's order or duplicates.  A pair found in
+ * no phenotype row is VAMPOMI_ERR_ARG (vampomi_last_error names the pair and
+ * its line).  drop_na != 0 also drops the rows whose value is "NA"; with
+ * drop_na == 0 an "NA" in a row that would be kept is VAMPOMI_ERR_NAN_PHEN.
+ * *N_file = the file's rows, *n = the kept rows (either may be NULL); rows
+ * (NULL: count only) receives them, cap < n is VAMPOMI_ERR_ARG.  A file that
+ * cannot be opened is VAMPOMI_ERR_IO. */
+vampomi_status vampomi_phen_rows(const char* phen_path, const char* keep_path, int drop_na, int64_t* rows,
+                                 int64_t cap, int64_t* N_file, int64_t* n);
 /* marker-major fp64 file (README.md:15): this shard's bytes [S*N*8, (S+M)*N*8).
  * On an F32 or U16 context each chunk is staged on the device as fp64 and
  * rounded (nearest even) or quantised (VAMPOMI_STORE_U16: range-checked,

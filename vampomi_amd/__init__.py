@@ -23,7 +23,7 @@ import numpy as np
 from ._lib import (CLI_PATH, GEN_GAUSS, GEN_METH, LIB_PATH, MAX_L, MEM_DEVICE, MEM_HOST, STORE_F32, STORE_F64,
                    STORE_U16, UNIQUE_ID_BYTES, Params, Result, ShardDesc, Stats, VampomiError, check, load)
 
-__all__ = ["Data", "Vamp", "VampOptions", "divide_work", "comm_unique_id", "VampomiError", "LIB_PATH", "CLI_PATH",
+__all__ = ["Data", "Vamp", "VampOptions", "divide_work", "comm_unique_id", "phen_rows", "VampomiError", "LIB_PATH", "CLI_PATH",
            "GEN_GAUSS", "GEN_METH", "STORE_F64", "STORE_F32", "STORE_U16", "load"]
 
 _STORAGE = {"f64": STORE_F64, "f32": STORE_F32, "u16": STORE_U16}
@@ -47,6 +47,23 @@ def comm_unique_id() -> bytes:
     return bytes(buf)
 
 
+def phen_rows(path: str, keep_file: Optional[str] = None, drop_na: bool = False):
+    """(rows, N_file): the ascending rows of the PLINK phenotype file ``path``
+    that an analysis keeps, and the file's row count (vampomi_phen_rows; no
+    device needed).  ``keep_file``: PLINK ``--keep`` style, FID and IID per
+    line; ``drop_na``: rows whose value is ``NA`` are dropped too (else an
+    ``NA`` in a kept row raises status 5).  Pass them as ``Data(N_file, Mt,
+    rows=rows)``."""
+    lib = load()
+    keep = None if keep_file is None else keep_file.encode()
+    nf, n = C.c_int64(), C.c_int64()
+    check(lib.vampomi_phen_rows(path.encode(), keep, 1 if drop_na else 0, None, 0, C.byref(nf), C.byref(n)))
+    rows = np.zeros(max(n.value, 1), dtype=np.int64)
+    check(lib.vampomi_phen_rows(path.encode(), keep, 1 if drop_na else 0, _dp(rows), n.value, C.byref(nf),
+                                C.byref(n)))
+    return rows[: n.value], nf.value
+
+
 class Data:
     """Device-resident marker shard + phenotype (reference ``class data``).
 
@@ -67,12 +84,26 @@ class Data:
     ``VampomiError`` (status 9, ``ERR_RANGE``; the message names the first such
     entry), and :meth:`quant_stats` tells what the quantisation did.  All
     arithmetic stays fp64.  The ``storage`` attribute tells which is in use.
+
+    ``rows``: a row subset (:func:`phen_rows`).  ``N`` is then the row count of
+    the FILES, the context is opened with ``len(rows)`` samples, ``d.N ==
+    len(rows)``, and ``d.N_file`` and ``d.rows`` tell the rest.  The loads
+    (:meth:`read_methylation_data`, :meth:`load_meth` with an ``(M, N_file)``
+    array, :meth:`read_phen`, :meth:`read_covariates`) take the full files and
+    keep those rows; the context then holds, bit for bit, what a plain one
+    holds after loading files with the other rows removed.  :meth:`set_phen`
+    and :meth:`set_covariates` keep taking ``d.N`` rows.
     """
 
     def __init__(self, N: int, Mt: int, rank: int = 0, nranks: int = 1, comm_id: Optional[bytes] = None,
-                 device: int = -1, alpha_scale: float = 1.0, storage: Optional[str] = None):
+                 device: int = -1, alpha_scale: float = 1.0, storage: Optional[str] = None,
+                 rows: Optional[Sequence[int]] = None):
         if storage is not None and storage not in _STORAGE:
             raise ValueError(f'storage must be "f64", "f32" or "u16", not {storage!r}')
+        self.N_file, self.rows = N, None
+        if rows is not None:
+            self.rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+            N = len(self.rows)
         self._lib = load()
         self._idbuf = None
         d = ShardDesc(N=N, Mt=Mt, rank=rank, nranks=nranks, device=device, comm_id=None, alpha_scale=alpha_scale)
@@ -91,6 +122,8 @@ class Data:
         self.M, self.S, self.ld = M.value, S.value, ld.value
         if storage is not None:
             check(self._lib.vampomi_set_storage(self.ctx, _STORAGE[storage]))
+        if self.rows is not None:
+            check(self._lib.vampomi_set_row_subset(self.ctx, self.N_file, _dp(self.rows), len(self.rows)))
 
     @property
     def storage(self) -> str:
@@ -145,7 +178,7 @@ class Data:
     def load_meth(self, X: np.ndarray):
         """X: (M, N), this shard's markers (marker-major): float64, float32
         (passed as it is, with no upcast copy) or uint16 (k meaning k / 65536),
-        for any storage."""
+        for any storage.  With a row subset: (M, N_file)."""
         if getattr(X, "dtype", None) == np.float32:
             X = np.ascontiguousarray(X)
             load_host = self._lib.vampomi_load_meth_host_f32
@@ -155,9 +188,9 @@ class Data:
         else:
             X = np.ascontiguousarray(X, dtype=np.float64)
             load_host = self._lib.vampomi_load_meth_host
-        if X.shape != (self.M, self.N):
-            raise ValueError(f"expected shard shape {(self.M, self.N)}, got {X.shape}")
-        check(load_host(self.ctx, _dp(X), self.N))
+        if X.shape != (self.M, self.N_file):
+            raise ValueError(f"expected shard shape {(self.M, self.N_file)}, got {X.shape}")
+        check(load_host(self.ctx, _dp(X), self.N_file))
 
     def generate(self, seed: int, kind: int = GEN_GAUSS):
         check(self._lib.vampomi_generate_meth(self.ctx, seed, kind))

@@ -110,6 +110,10 @@ SIGNATURES = {
     "vampomi_barrier_timeout": (C.c_int, [_P, C.c_double]),
     "vampomi_set_storage": (C.c_int, [_P, C.c_int]),
     "vampomi_get_storage": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "vampomi_set_row_subset": (C.c_int, [_P, C.c_int64, _P, C.c_int64]),
+    "vampomi_get_row_subset": (C.c_int, [_P, C.POINTER(C.c_int64), _P]),
+    "vampomi_phen_rows": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64),
+                                    C.POINTER(C.c_int64)]),
     "vampomi_load_meth_file": (C.c_int, [_P, C.c_char_p]),
     "vampomi_load_meth_file_f32": (C.c_int, [_P, C.c_char_p]),
     "vampomi_load_meth_host": (C.c_int, [_P, _P, C.c_int64]),

@@ -213,7 +213,16 @@ extern "C" vampomi_status vampomi_read_covariates(vampomi_ctx* c, const char* pa
         return fail(VAMPOMI_ERR_ARG, "number of covariates out of range (0.." + std::to_string(VAMPOMI_MAX_C) + ")");
     HIPCHK(hipSetDevice(c->device));
     std::vector<double> Z((size_t)C * (size_t)c->N);
-    STCHK(vampomi_parse_covariates(path, c->N, C, 1, Z.data()));
+    if (c->N_file && C > 0) {  // the file's N_file rows raw, the subset's kept, then standardised
+        std::vector<double> raw((size_t)C * (size_t)c->N_file);
+        STCHK(vampomi_parse_covariates(path, c->N_file, C, 0, raw.data()));
+        for (int j = 0; j < C; ++j)
+            for (int64_t i = 0; i < c->N; ++i)
+                Z[(size_t)j * c->N + i] = raw[(size_t)j * c->N_file + c->rows_host[(size_t)i]];
+        vio::standardize_covariates(Z.data(), c->N, C, c->N);
+    } else {
+        STCHK(vampomi_parse_covariates(path, c->N, C, 1, Z.data()));
+    }
     c->cov_host.swap(Z);
     return upload_cov(c, C);
 }

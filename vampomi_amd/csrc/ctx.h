@@ -102,6 +102,12 @@ struct vampomi_ctx {
     vk::QuantRec* qrec = nullptr;
     int64_t q_clamped = 0;
     double q_max_err = 0.0;
+    // the row subset (vampomi_set_row_subset; N_file == 0: none): the files hold
+    // N_file rows of which rows_host (N ascending indices) are loaded; rows_dev:
+    // their device copy for vk::gather_cols
+    int64_t N_file = 0;
+    std::vector<int64_t> rows_host;
+    int32_t* rows_dev = nullptr;
     double* mave = nullptr;
     double* msig = nullptr;
     double* y = nullptr;     // ld, zero pad

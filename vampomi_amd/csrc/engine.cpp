@@ -1129,6 +1129,8 @@ void release_ctx_resources(vampomi_ctx* c) {
     c->X = nullptr;
     if (c->qrec) (void)hipFree(c->qrec);
     c->qrec = nullptr;
+    if (c->rows_dev) (void)hipFree(c->rows_dev);
+    c->rows_dev = nullptr;
     for (double** p : {&c->mave, &c->msig, &c->y, &c->ax_part, &c->red_part, &c->scal, &c->nbuf, &c->mbuf,
                        &c->op_part, &c->op_nvec, &c->cov_Z, &c->cov_part, &c->cov_dev})
         dev_free(*p);
@@ -1326,6 +1328,44 @@ extern "C" vampomi_status vampomi_get_storage(const vampomi_ctx* c, int* storage
     return VAMPOMI_OK;
 }
 
+extern "C" vampomi_status vampomi_set_row_subset(vampomi_ctx* c, int64_t N_file, const int64_t* rows, int64_t n) {
+    if (!c || !rows) return fail(VAMPOMI_ERR_ARG, "null argument");
+    if (c->X) return fail(VAMPOMI_ERR_STATE, "the row subset is fixed once the methylation shard is allocated");
+    if (c->have_y || c->cov_C > 0)
+        return fail(VAMPOMI_ERR_STATE, "set the row subset before the phenotype and the covariates");
+    if (N_file >= ((int64_t)1 << 31)) return fail(VAMPOMI_ERR_ARG, "row subset: N_file must be below 2^31");
+    if (n != c->N)
+        return fail(VAMPOMI_ERR_ARG, "row subset: n (" + std::to_string(n) + ") != the context's N (" +
+                                         std::to_string(c->N) + "): open the context with N = n");
+    if (n < 2 || n > N_file) return fail(VAMPOMI_ERR_ARG, "row subset: 2 <= n <= N_file");
+    for (int64_t j = 0; j < n; ++j)
+        if (rows[j] < 0 || rows[j] >= N_file || (j > 0 && rows[j] <= rows[j - 1]))
+            return fail(VAMPOMI_ERR_ARG, "row subset: rows must be strictly ascending within [0, N_file) (entry " +
+                                             std::to_string(j) + " is " + std::to_string(rows[j]) + ")");
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->rows_dev && hipMalloc((void**)&c->rows_dev, (size_t)n * sizeof(int32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        c->rows_dev = nullptr;
+        return fail(VAMPOMI_ERR_OOM, "row subset");
+    }
+    const std::vector<int32_t> r32(rows, rows + n);
+    HIPCHK(hipMemcpyAsync(c->rows_dev, r32.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    c->rows_host.assign(rows, rows + n);
+    c->N_file = N_file;
+    return VAMPOMI_OK;
+}
+
+extern "C" vampomi_status vampomi_get_row_subset(const vampomi_ctx* c, int64_t* N_file, int64_t* rows) {
+    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
+    if (N_file) *N_file = c->N_file;
+    if (rows && c->N_file) std::memcpy(rows, c->rows_host.data(), c->rows_host.size() * sizeof(int64_t));
+    return VAMPOMI_OK;
+}
+
+// the rows of a column of the input: the file's with a row subset, else N
+static int64_t rows_in(const vampomi_ctx* c) { return c->N_file ? c->N_file : c->N; }
+
 static vampomi_status finish_X(vampomi_ctx* c) {
     const size_t es = (size_t)c->esize();
     if (c->ld > c->N && c->M > 0)
@@ -1371,8 +1411,8 @@ static vampomi_status quant_end(vampomi_ctx* c) {
     HIPCHK(hipStreamSynchronize(c->st));
     if (r.rejected) {
         c->have_X = false;
-        const long long marker = (long long)(r.first / (unsigned long long)c->N);
-        const long long row = (long long)(r.first % (unsigned long long)c->N);
+        const long long marker = (long long)(r.first / (unsigned long long)rows_in(c));
+        const long long row = (long long)(r.first % (unsigned long long)rows_in(c));  // (the file's row)
         return fail(VAMPOMI_ERR_RANGE,
                     std::to_string(r.rejected) + " methylation value(s) cannot be stored as 16-bit fixed point (NaN, "
                     "infinite, below 0 or above 1); the first is marker " + std::to_string(marker) + ", row " +
@@ -1400,18 +1440,21 @@ extern "C" vampomi_status vampomi_get_quant_stats(const vampomi_ctx* c, int64_t*
 // on the 2^-16 grid, range-checked into c->qrec):
 // *stage (cap_bytes; grown as needed, freed by the caller) is that buffer.  All
 // on the context's stream, so the caller may reuse src once the stream has
-// passed this point.
+// passed this point.  With a row subset the block's columns hold N_file
+// elements and every block takes the staging hop: vk::gather_cols keeps the
+// subset's rows as it converts (or copies).
 static vampomi_status put_cols(vampomi_ctx* c, int64_t i0, int64_t nc, const void* src, int64_t ld_in, int in_es,
                                void** stage, size_t* cap_bytes) {
     if (nc <= 0) return VAMPOMI_OK;
     const size_t es = (size_t)c->esize();
     char* dst = (char*)c->X + (size_t)i0 * (size_t)c->ld * es;
-    if ((size_t)in_es == es) {
+    if ((size_t)in_es == es && !c->N_file) {
         HIPCHK(hipMemcpy2DAsync(dst, (size_t)c->ld * es, src, (size_t)ld_in * es, (size_t)c->N * es, (size_t)nc,
                                 hipMemcpyHostToDevice, c->st));
         return VAMPOMI_OK;
     }
-    const size_t need = (size_t)nc * (size_t)c->N * (size_t)in_es;
+    const int64_t Nin = rows_in(c);
+    const size_t need = (size_t)nc * (size_t)Nin * (size_t)in_es;
     if (*cap_bytes < need) {
         HIPCHK(hipStreamSynchronize(c->st));
         if (*stage) (void)hipFree(*stage);
@@ -1423,9 +1466,12 @@ static vampomi_status put_cols(vampomi_ctx* c, int64_t i0, int64_t nc, const voi
         }
         *cap_bytes = need;
     }
-    HIPCHK(hipMemcpy2DAsync(*stage, (size_t)c->N * in_es, src, (size_t)ld_in * in_es, (size_t)c->N * in_es,
+    HIPCHK(hipMemcpy2DAsync(*stage, (size_t)Nin * in_es, src, (size_t)ld_in * in_es, (size_t)Nin * in_es,
                             (size_t)nc, hipMemcpyHostToDevice, c->st));
-    if (es == 2 && in_es == 8)
+    if (c->N_file)
+        HIPCHK(vk::gather_cols(*stage, in_es == 2 ? vk::kXU16 : in_es == 4 ? vk::kXF32 : vk::kXF64, Nin, c->rows_dev,
+                               c->N, nc, dst, c->ek(), c->ld, Nin, c->S + i0, c->qrec, c->st));
+    else if (es == 2 && in_es == 8)
         HIPCHK(vk::quantise_cols((const double*)*stage, c->N, c->N, nc, (uint16_t*)dst, c->ld, c->S + i0, c->qrec,
                                  c->st));
     else if (es == 2)
@@ -1446,16 +1492,16 @@ static vampomi_status put_cols(vampomi_ctx* c, int64_t i0, int64_t nc, const voi
 // chunks of about 256 MB where it has to be converted (put_cols' staging
 // buffer)
 static vampomi_status load_host(vampomi_ctx* c, const void* X, int64_t ld_in, int in_es) {
-    if (!c || (!X && c->M > 0) || ld_in < c->N) return fail(VAMPOMI_ERR_ARG, "invalid host shard");
+    if (!c || (!X && c->M > 0) || ld_in < rows_in(c)) return fail(VAMPOMI_ERR_ARG, "invalid host shard");
     HIPCHK(hipSetDevice(c->device));
     STCHK(ensure_X(c));
     STCHK(quant_begin(c));
     void* stage = nullptr;
     size_t cap = 0;
     vampomi_status st = VAMPOMI_OK;
-    const int64_t chunk = (int64_t)in_es == c->esize()
+    const int64_t chunk = (int64_t)in_es == c->esize() && !c->N_file
                               ? std::max<int64_t>(c->M, 1)
-                              : std::max<int64_t>(1, io_chunk_bytes() / (c->N * in_es));
+                              : std::max<int64_t>(1, io_chunk_bytes() / (rows_in(c) * in_es));
     for (int64_t i0 = 0; i0 < c->M && st == VAMPOMI_OK; i0 += chunk)
         st = put_cols(c, i0, std::min(chunk, c->M - i0), (const char*)X + (size_t)i0 * (size_t)ld_in * in_es, ld_in,
                       in_es, &stage, &cap);
@@ -1530,7 +1576,7 @@ static vampomi_status load_file(vampomi_ctx* c, const char* path, int in_es) {
         ::close(fd);
         return s0;
     }
-    const size_t colb = (size_t)c->N * (size_t)in_es;
+    const size_t colb = (size_t)rows_in(c) * (size_t)in_es;
     const size_t chunk_cols = std::max<size_t>(1, (size_t)io_chunk_bytes() / colb);
     const char* env = std::getenv("VAMPOMI_IO_THREADS");
     const int nt = env ? std::max(1, std::atoi(env)) : (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
@@ -1560,7 +1606,7 @@ static vampomi_status load_file(vampomi_ctx* c, const char* path, int in_es) {
             st = fail(VAMPOMI_ERR_IO, std::string("short read from methylation file ") + path);
             break;
         }
-        st = put_cols(c, i0, nc, pin[b], c->N, in_es, &stage, &stage_cap);
+        st = put_cols(c, i0, nc, pin[b], rows_in(c), in_es, &stage, &stage_cap);
         if (st != VAMPOMI_OK) break;
         if (hipEventRecord(done[b], c->st) != hipSuccess) {
             st = fail(VAMPOMI_ERR_HIP, "host-to-device copy of the methylation shard");
@@ -1594,6 +1640,7 @@ extern "C" vampomi_status vampomi_load_meth_file_u16(vampomi_ctx* c, const char*
 
 extern "C" vampomi_status vampomi_generate_meth(vampomi_ctx* c, uint64_t seed, int kind) {
     if (!c || (kind != VAMPOMI_GEN_GAUSS && kind != VAMPOMI_GEN_METH)) return fail(VAMPOMI_ERR_ARG, "bad argument");
+    if (c->N_file) return fail(VAMPOMI_ERR_STATE, "a context with a row subset loads its shard from a file or the host");
     if (c->u16() && kind == VAMPOMI_GEN_GAUSS)
         return fail(VAMPOMI_ERR_RANGE, "VAMPOMI_GEN_GAUSS values are not in [0, 1]: they cannot be stored as 16-bit "
                                        "fixed point (VAMPOMI_STORE_U16)");
@@ -1639,11 +1686,26 @@ extern "C" vampomi_status vampomi_read_phen(vampomi_ctx* c, const char* path, in
     if (!c || !path) return fail(VAMPOMI_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(c->device));
     std::vector<double> y;
-    const int64_t n = vio::read_phen(path, y);
-    if (n == -1) return fail(VAMPOMI_ERR_IO, std::string("FATAL: could not open phenotype file: ") + path);
-    if (n == -2) return fail(VAMPOMI_ERR_NAN_PHEN, "NAN in data!");
-    if (n != c->N)
-        return fail(VAMPOMI_ERR_ARG, "phenotype rows (" + std::to_string(n) + ") != N (" + std::to_string(c->N) + ")");
+    if (c->N_file) {  // the file's N_file rows, of which the subset's are kept: NA only matters there
+        vio::PhenTable t;
+        if (!vio::read_phen_table(path, t))
+            return fail(VAMPOMI_ERR_IO, std::string("FATAL: could not open phenotype file: ") + path);
+        if ((int64_t)t.value.size() != c->N_file)
+            return fail(VAMPOMI_ERR_ARG, "phenotype rows (" + std::to_string(t.value.size()) + ") != N_file (" +
+                                             std::to_string(c->N_file) + ")");
+        y.reserve((size_t)c->N);
+        for (const int64_t r : c->rows_host) {
+            if (t.na[(size_t)r]) return fail(VAMPOMI_ERR_NAN_PHEN, "NAN in data!");
+            y.push_back(t.value[(size_t)r]);
+        }
+    } else {
+        const int64_t n = vio::read_phen(path, y);
+        if (n == -1) return fail(VAMPOMI_ERR_IO, std::string("FATAL: could not open phenotype file: ") + path);
+        if (n == -2) return fail(VAMPOMI_ERR_NAN_PHEN, "NAN in data!");
+        if (n != c->N)
+            return fail(VAMPOMI_ERR_ARG,
+                        "phenotype rows (" + std::to_string(n) + ") != N (" + std::to_string(c->N) + ")");
+    }
     if (standardize) vio::standardize_phen(y);
     c->y_host = y;
     return upload_phen(c);
@@ -1661,6 +1723,29 @@ extern "C" vampomi_status vampomi_get_phen(vampomi_ctx* c, double* y) {
     if (!c || !y) return fail(VAMPOMI_ERR_ARG, "null argument");
     if (!c->have_y) return fail(VAMPOMI_ERR_STATE, "no phenotype loaded");
     std::memcpy(y, c->y_host.data(), (size_t)c->N * 8);
+    return VAMPOMI_OK;
+}
+
+extern "C" vampomi_status vampomi_phen_rows(const char* phen_path, const char* keep_path, int drop_na, int64_t* rows,
+                                            int64_t cap, int64_t* N_file, int64_t* n) {
+    if (!phen_path) return fail(VAMPOMI_ERR_ARG, "null argument");
+    std::vector<int64_t> kept;
+    int64_t nfile = 0;
+    std::string err;
+    switch (vio::phen_rows(phen_path, keep_path ? keep_path : "", drop_na != 0, kept, &nfile, nullptr, nullptr, &err)) {
+        case 0: break;
+        case -1: return fail(VAMPOMI_ERR_IO, err);
+        case -2: return fail(VAMPOMI_ERR_NAN_PHEN, err);
+        default: return fail(VAMPOMI_ERR_ARG, err);
+    }
+    if (N_file) *N_file = nfile;
+    if (n) *n = (int64_t)kept.size();
+    if (rows) {
+        if (cap < (int64_t)kept.size())
+            return fail(VAMPOMI_ERR_ARG, "rows holds " + std::to_string(cap) + " entries, " +
+                                             std::to_string(kept.size()) + " rows are kept");
+        std::copy(kept.begin(), kept.end(), rows);
+    }
     return VAMPOMI_OK;
 }
 

@@ -11,6 +11,8 @@
 #include <cstring>
 #include <chrono>
 #include <fstream>
+#include <map>
+#include <set>
 #include <thread>
 
 #include <sys/stat.h>
@@ -55,6 +57,88 @@ int64_t read_phen(const std::string& path, std::vector<double>& y) {
         y.push_back(std::atof(tok[2].c_str()));
     }
     return (int64_t)y.size();
+}
+
+bool read_phen_table(const std::string& path, PhenTable& t) {
+    std::ifstream in(path);
+    if (!in.is_open()) return false;
+    t = PhenTable();
+    std::string line;
+    std::vector<std::string> tok;
+    while (std::getline(in, line)) {
+        split_ws(line, tok);  // read_phen's rows: the lines with a third token
+        if (tok.size() < 3) continue;
+        const bool na = tok[2] == "NA";
+        t.fid.push_back(tok[0]);
+        t.iid.push_back(tok[1]);
+        t.na.push_back(na ? 1 : 0);
+        t.value.push_back(na ? 0.0 : std::atof(tok[2].c_str()));
+    }
+    return true;
+}
+
+int phen_rows(const std::string& phen_path, const std::string& keep_path, bool drop_na, std::vector<int64_t>& rows,
+              int64_t* N_file, int64_t* not_kept, int64_t* na_dropped, std::string* err) {
+    PhenTable t;
+    if (!read_phen_table(phen_path, t)) {
+        *err = "FATAL: could not open phenotype file: " + phen_path;
+        return -1;
+    }
+    typedef std::pair<std::string, std::string> Id;
+    std::map<Id, int64_t> keep;  // the pair and the first line that names it
+    if (!keep_path.empty()) {
+        std::ifstream in(keep_path);
+        if (!in.is_open()) {
+            *err = "FATAL: could not open keep file: " + keep_path;
+            return -1;
+        }
+        std::string line;
+        std::vector<std::string> tok;
+        int64_t lineno = 0;
+        while (std::getline(in, line)) {
+            ++lineno;
+            bool blank = true;
+            for (const char ch : line) blank = blank && is_ws(ch);
+            if (blank) continue;
+            split_ws(line, tok);
+            if (tok.size() < 2) {
+                *err = "keep file " + keep_path + ", line " + std::to_string(lineno) + ": expected FID and IID";
+                return -3;
+            }
+            keep.emplace(Id(tok[0], tok[1]), lineno);
+        }
+        std::set<Id> have;
+        for (size_t i = 0; i < t.fid.size(); ++i) have.insert(Id(t.fid[i], t.iid[i]));
+        const std::pair<const Id, int64_t>* missing = nullptr;  // the one named first in the keep file
+        for (const auto& k : keep)
+            if (!have.count(k.first) && (!missing || k.second < missing->second)) missing = &k;
+        if (missing) {
+            *err = "keep file " + keep_path + ", line " + std::to_string(missing->second) + ": no individual \"" +
+                   missing->first.first + " " + missing->first.second + "\" in phenotype file " + phen_path;
+            return -3;
+        }
+    }
+    rows.clear();
+    int64_t out = 0, nas = 0;
+    for (size_t i = 0; i < t.value.size(); ++i) {
+        if (!keep_path.empty() && !keep.count(Id(t.fid[i], t.iid[i]))) {
+            ++out;
+            continue;
+        }
+        if (t.na[i]) {
+            if (!drop_na) {
+                *err = "NAN in data!";
+                return -2;
+            }
+            ++nas;
+            continue;
+        }
+        rows.push_back((int64_t)i);
+    }
+    if (N_file) *N_file = (int64_t)t.value.size();
+    if (not_kept) *not_kept = out;
+    if (na_dropped) *na_dropped = nas;
+    return 0;
 }
 
 void standardize_covariates(double* Z, int64_t N, int C, int64_t ld) {

@@ -13,6 +13,27 @@ int64_t read_phen(const std::string& path, std::vector<double>& y);
 // (src/data.cpp:97-104).  Returns the scale factor.
 double standardize_phen(std::vector<double>& y);
 
+// read_phen's rows with their IDs, "NA" kept as a flag instead of ending the
+// read: fid / iid are tokens 0 and 1 of the same split, na[i] says token 2 ==
+// "NA" (value[i] is then 0).  False: cannot open.
+struct PhenTable {
+    std::vector<std::string> fid, iid;
+    std::vector<double> value;
+    std::vector<char> na;
+};
+bool read_phen_table(const std::string& path, PhenTable& t);
+// The rows of a phenotype file that an analysis keeps, ascending.  keep_path
+// ("" for none): PLINK --keep style, per non-blank line FID and IID (tokens 0
+// and 1 of read_phen's split, further fields ignored); a row is kept iff its
+// pair is named, whatever the keep file's order or duplicates.  drop_na: rows
+// with "NA" are dropped too; else an "NA" in a row that would be kept is an
+// error.  0 ok; -1 a file cannot be opened; -2 that "NA"; -3 a keep line
+// without two fields, or a pair that is in no phenotype row (*err names the
+// pair and its line).  *N_file: the file's rows; *not_kept / *na_dropped: the
+// rows the keep file and the "NA"s took out (each may be null).
+int phen_rows(const std::string& phen_path, const std::string& keep_path, bool drop_na, std::vector<int64_t>& rows,
+              int64_t* N_file, int64_t* not_kept, int64_t* na_dropped, std::string* err);
+
 // data::read_covariates (src/data.cpp:159-227): a header line, then per row
 // two IDs and exactly C numeric fields, split like read_phen's.  out: C
 // columns of N (covariate-major).  0 ok; -1 cannot open; -2 a row without

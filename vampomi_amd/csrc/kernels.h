@@ -318,6 +318,19 @@ hipError_t dequant_cols(const uint16_t* src, int64_t lds, int64_t N, int64_t nco
                         hipStream_t st);
 hipError_t dequant_cols(const uint16_t* src, int64_t lds, int64_t N, int64_t ncols, float* dst, int64_t ldd,
                         hipStream_t st);
+// ---- row subset: the conversions above with a row gather ------------------------
+// dst[c*ldd + j] = conv(src[c*lds + rows[j]]), j < n, c < ncols, for a staged
+// chunk of packed columns of nfile elements (lds >= nfile; a column is only as
+// aligned as its element) and n ascending device indices rows[j] in
+// [0, nfile).  src_ek / dst_ek (kXF64 / kXF32 / kXU16) pick conv: exactly what
+// narrow_cols, widen_cols, dequant_cols and quantise_cols store, and a copy
+// where the kinds agree, so the stored bits are those of the conversion of the
+// chunk with the other rows taken out beforehand.  Into kXU16 from doubles or
+// floats, *rec takes the kept entries only, its first as
+// (col0 + c) * nfile + rows[j] (the file's row); rec is not read otherwise
+hipError_t gather_cols(const void* src, int src_ek, int64_t lds, const int32_t* rows, int64_t n, int64_t ncols,
+                       void* dst, int dst_ek, int64_t ldd, int64_t nfile, int64_t col0, QuantRec* rec,
+                       hipStream_t st);
 // beta_i = gauss(seed) for causal markers (uniform < lam), else 0; the count
 // of causal markers in ro.out[0]
 hipError_t gen_beta(uint64_t seed, double lam, int64_t S, int64_t M, double* beta, const RedOut& ro, hipStream_t st);

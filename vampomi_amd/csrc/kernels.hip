@@ -1602,16 +1602,11 @@ __global__ __launch_bounds__(kBlock) void widen_kernel(const float* __restrict__
 // lanes saw (integer sums, a minimum, a maximum of non-negative doubles, which
 // order as their bit patterns do) and lane 0 adds it to *rec with ordinary
 // atomics, so the record does not depend on the order anything ran in.
-template <class XS>
-__global__ __launch_bounds__(kBlock) void quantise_kernel(const XS* __restrict__ src, int64_t lds, int64_t N,
-                                                          int64_t ncols, uint16_t* __restrict__ dst, int64_t ldd,
-                                                          int64_t col0, QuantRec* __restrict__ rec) {
-    const int64_t total = N * ncols;
+struct QuantAcc {
     unsigned long long rejected = 0, clamped = 0, first = ~0ull;
     double err = 0.0;
-    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += (int64_t)gridDim.x * kBlock) {
-        const int64_t c = e / N, j = e - c * N;
-        const double x = (double)src[c * lds + j];
+    // the stored element of x; at: the entry's index for rec->first
+    __device__ uint16_t put(double x, unsigned long long at) {
         unsigned k = 0;
         if (x >= 0.0 && x <= 1.0) {
             const double r = __builtin_rint(x * 65536.0);
@@ -1625,28 +1620,43 @@ __global__ __launch_bounds__(kBlock) void quantise_kernel(const XS* __restrict__
             err = d > err ? d : err;
         } else {
             ++rejected;
-            const unsigned long long at = (unsigned long long)((col0 + c) * N + j);
             first = at < first ? at : first;
         }
-        dst[c * ldd + j] = (uint16_t)k;
+        return (uint16_t)k;
     }
-    unsigned long long eb = (unsigned long long)__double_as_longlong(err);
+    // every lane of the wave, once, after its last put
+    __device__ void flush(QuantRec* __restrict__ rec) {
+        unsigned long long eb = (unsigned long long)__double_as_longlong(err);
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        rejected += __shfl_xor(rejected, o, 64);
-        clamped += __shfl_xor(clamped, o, 64);
-        const unsigned long long f = __shfl_xor(first, o, 64), m = __shfl_xor(eb, o, 64);
-        first = f < first ? f : first;
-        eb = m > eb ? m : eb;
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (rejected) {
-            atomicAdd(&rec->rejected, rejected);
-            atomicMin(&rec->first, first);
+        for (int o = 32; o > 0; o >>= 1) {
+            rejected += __shfl_xor(rejected, o, 64);
+            clamped += __shfl_xor(clamped, o, 64);
+            const unsigned long long f = __shfl_xor(first, o, 64), m = __shfl_xor(eb, o, 64);
+            first = f < first ? f : first;
+            eb = m > eb ? m : eb;
         }
-        if (clamped) atomicAdd(&rec->clamped, clamped);
-        if (eb) atomicMax(&rec->max_err, eb);
+        if ((threadIdx.x & 63) == 0) {
+            if (rejected) {
+                atomicAdd(&rec->rejected, rejected);
+                atomicMin(&rec->first, first);
+            }
+            if (clamped) atomicAdd(&rec->clamped, clamped);
+            if (eb) atomicMax(&rec->max_err, eb);
+        }
     }
+};
+
+template <class XS>
+__global__ __launch_bounds__(kBlock) void quantise_kernel(const XS* __restrict__ src, int64_t lds, int64_t N,
+                                                          int64_t ncols, uint16_t* __restrict__ dst, int64_t ldd,
+                                                          int64_t col0, QuantRec* __restrict__ rec) {
+    const int64_t total = N * ncols;
+    QuantAcc acc;
+    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += (int64_t)gridDim.x * kBlock) {
+        const int64_t c = e / N, j = e - c * N;
+        dst[c * ldd + j] = acc.put((double)src[c * lds + j], (unsigned long long)((col0 + c) * N + j));
+    }
+    acc.flush(rec);
 }
 
 template <class XS>
@@ -1717,6 +1727,98 @@ hipError_t widen_cols(const float* src, int64_t lds, int64_t N, int64_t ncols, d
     if (lds < N || ldd < N) return hipErrorInvalidValue;
     const int64_t blocks = std::min<int64_t>(cdiv(N * ncols, kBlock), 65536);
     hipLaunchKernelGGL(widen_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, src, lds, N, ncols, dst, ldd);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// row subset: the ingest conversions with a row gather
+// ---------------------------------------------------------------------------
+// what the conversion kernels above store for one element (the identity where
+// the types agree)
+template <class XD, class XS>
+__device__ __forceinline__ XD ingest_conv(XS x) {
+    return (XD)x;
+}
+template <>
+__device__ __forceinline__ double ingest_conv<double, uint16_t>(uint16_t k) {
+    return (double)k * 0x1p-16;
+}
+template <>
+__device__ __forceinline__ float ingest_conv<float, uint16_t>(uint16_t k) {
+    return (float)((double)k * 0x1p-16);
+}
+
+// dst[c*ldd + j] = conv(src[c*lds + rows[j]]), j < n, c < ncols.  The source
+// columns are packed (lds = the file's rows), so a column starts only as
+// aligned as its element: one element per load
+template <class XS, class XD>
+__global__ __launch_bounds__(kBlock) void gather_kernel(const XS* __restrict__ src, int64_t lds,
+                                                        const int32_t* __restrict__ rows, int64_t n, int64_t ncols,
+                                                        XD* __restrict__ dst, int64_t ldd) {
+    const int64_t total = n * ncols;
+    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += (int64_t)gridDim.x * kBlock) {
+        const int64_t c = e / n, j = e - c * n;
+        dst[c * ldd + j] = ingest_conv<XD, XS>(src[c * lds + rows[j]]);
+    }
+}
+
+// quantise_kernel over the kept rows only: what a dropped row holds is neither
+// stored, rejected nor counted; rec->first is (col0 + c) * nfile + rows[j]
+template <class XS>
+__global__ __launch_bounds__(kBlock) void gather_quantise_kernel(const XS* __restrict__ src, int64_t lds,
+                                                                 const int32_t* __restrict__ rows, int64_t n,
+                                                                 int64_t ncols, uint16_t* __restrict__ dst,
+                                                                 int64_t ldd, int64_t nfile, int64_t col0,
+                                                                 QuantRec* __restrict__ rec) {
+    const int64_t total = n * ncols;
+    QuantAcc acc;
+    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += (int64_t)gridDim.x * kBlock) {
+        const int64_t c = e / n, j = e - c * n;
+        const int64_t r = rows[j];
+        dst[c * ldd + j] = acc.put((double)src[c * lds + r], (unsigned long long)((col0 + c) * nfile + r));
+    }
+    acc.flush(rec);
+}
+
+template <class XS, class XD>
+static void gather_launch(const void* src, int64_t lds, const int32_t* rows, int64_t n, int64_t ncols, void* dst,
+                          int64_t ldd, unsigned blocks, hipStream_t st) {
+    hipLaunchKernelGGL((gather_kernel<XS, XD>), dim3(blocks), dim3(kBlock), 0, st, static_cast<const XS*>(src), lds,
+                       rows, n, ncols, static_cast<XD*>(dst), ldd);
+}
+
+hipError_t gather_cols(const void* src, int src_ek, int64_t lds, const int32_t* rows, int64_t n, int64_t ncols,
+                       void* dst, int dst_ek, int64_t ldd, int64_t nfile, int64_t col0, QuantRec* rec,
+                       hipStream_t st) {
+    if (n <= 0 || ncols <= 0) return hipSuccess;
+    if (!rows || n > nfile || lds < nfile || ldd < n) return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)std::min<int64_t>(cdiv(n * ncols, kBlock), 65536);
+    if (dst_ek == kXU16 && src_ek != kXU16) {
+        if (!rec) return hipErrorInvalidValue;
+        if (src_ek == kXF64)
+            hipLaunchKernelGGL(gather_quantise_kernel<double>, dim3(blocks), dim3(kBlock), 0, st,
+                               static_cast<const double*>(src), lds, rows, n, ncols, static_cast<uint16_t*>(dst), ldd,
+                               nfile, col0, rec);
+        else
+            hipLaunchKernelGGL(gather_quantise_kernel<float>, dim3(blocks), dim3(kBlock), 0, st,
+                               static_cast<const float*>(src), lds, rows, n, ncols, static_cast<uint16_t*>(dst), ldd,
+                               nfile, col0, rec);
+        return hipGetLastError();
+    }
+    if (src_ek == kXF64 && dst_ek == kXF64)
+        gather_launch<double, double>(src, lds, rows, n, ncols, dst, ldd, blocks, st);
+    else if (src_ek == kXF64)
+        gather_launch<double, float>(src, lds, rows, n, ncols, dst, ldd, blocks, st);
+    else if (src_ek == kXF32 && dst_ek == kXF64)
+        gather_launch<float, double>(src, lds, rows, n, ncols, dst, ldd, blocks, st);
+    else if (src_ek == kXF32)
+        gather_launch<float, float>(src, lds, rows, n, ncols, dst, ldd, blocks, st);
+    else if (dst_ek == kXF64)
+        gather_launch<uint16_t, double>(src, lds, rows, n, ncols, dst, ldd, blocks, st);
+    else if (dst_ek == kXF32)
+        gather_launch<uint16_t, float>(src, lds, rows, n, ncols, dst, ldd, blocks, st);
+    else
+        gather_launch<uint16_t, uint16_t>(src, lds, rows, n, ncols, dst, ldd, blocks, st);
     return hipGetLastError();
 }
 

@@ -172,6 +172,39 @@ int main(int argc, char** argv) {
         return EXIT_FAILURE;
     }
 
+    // --keep-file / --phen-na drop: the rows of the files that the run keeps,
+    // on the host and on every rank before any device call, so that a bad keep
+    // file or an NA that is fatal ends the job here on all of them.  --N /
+    // --N-test stay the files' rows; the context is opened with the kept ones
+    const bool test_mode = opt.run_mode == "test";  // the context holds the TEST data set (:128)
+    const std::string& keep = test_mode ? opt.keep_file_test : opt.keep_file;
+    const bool subset = !keep.empty() || opt.phen_na == "drop";
+    const int64_t N_file = test_mode ? opt.N_test : opt.N;
+    std::vector<int64_t> rows;
+    if (subset) {
+        int64_t nf = 0, out = 0, nas = 0;
+        std::string err;
+        if (vio::phen_rows(test_mode ? opt.phen_file_test : opt.phen_file, keep, opt.phen_na == "drop", rows, &nf, &out,
+                           &nas, &err) != 0) {
+            std::cout << "FATAL  : sample subset: " << err << std::endl;
+            return EXIT_FAILURE;
+        }
+        if (nf != N_file) {
+            std::cout << "FATAL  : sample subset: the phenotype file has " << nf << " rows, "
+                      << (test_mode ? "--N-test" : "--N") << " is " << N_file << std::endl;
+            return EXIT_FAILURE;
+        }
+        if (rows.size() < 2) {
+            std::cout << "FATAL  : sample subset: " << rows.size() << " of " << N_file
+                      << " samples are kept (at least 2 are needed)" << std::endl;
+            return EXIT_FAILURE;
+        }
+        if (rank == 0)
+            std::cout << "INFO   : kept " << rows.size() << " of " << N_file << " samples (" << out
+                      << " not in the keep file, " << nas << " with an NA phenotype)" << std::endl;
+    }
+    const int64_t n = subset ? (int64_t)rows.size() : N_file;
+
     // data::read_covariates (src/data.cpp:159-227), on every rank, before any
     // device call: a malformed table ends the job here as it ends the
     // reference's (every rank reads the same file and fails alike).  Only the
@@ -180,8 +213,16 @@ int main(int argc, char** argv) {
     std::vector<double> covs;
     if (use_cov) {
         if (opt.C <= VAMPOMI_MAX_C) covs.assign((size_t)opt.C * (size_t)opt.N, 0.0);
-        if (vampomi_parse_covariates(opt.cov_file.c_str(), (int64_t)opt.N, (int)opt.C, 1, covs.data()) != VAMPOMI_OK)
+        // (with a subset: raw, the kept rows are taken and standardised below)
+        if (vampomi_parse_covariates(opt.cov_file.c_str(), (int64_t)opt.N, (int)opt.C, subset ? 0 : 1, covs.data()) !=
+            VAMPOMI_OK)
             return die("covariates");
+        if (subset && opt.C <= VAMPOMI_MAX_C) {
+            std::vector<double> kept((size_t)opt.C * (size_t)n);
+            for (unsigned j = 0; j < opt.C; ++j)
+                for (int64_t i = 0; i < n; ++i) kept[(size_t)j * n + i] = covs[(size_t)j * opt.N + rows[(size_t)i]];
+            covs.swap(kept);
+        }
     } else if (opt.run_mode == "infere" && opt.C > 0 && rank == 0) {
         std::cout << "INFO   : --C " << opt.C << ": covariates are used by --model bin_class only and are ignored"
                   << std::endl;
@@ -198,9 +239,8 @@ int main(int argc, char** argv) {
         if (!exchange_id(path, rank, t_start - 120.0, id)) return die("communicator rendezvous failed");
         rdzv_path = path;
     }
-    const bool test_mode = opt.run_mode == "test";  // the context holds the TEST data set (:128)
     vampomi_shard_desc d{};
-    d.N = test_mode ? opt.N_test : opt.N;
+    d.N = n;
     d.Mt = opt.Mt;
     d.rank = rank;
     d.nranks = nranks;
@@ -216,6 +256,7 @@ int main(int argc, char** argv) {
                                  : opt.meth_storage == "f32" ? VAMPOMI_STORE_F32
                                                              : VAMPOMI_STORE_F64) != VAMPOMI_OK)
         return die("methylation storage");
+    if (subset && vampomi_set_row_subset(ctx, N_file, rows.data(), n) != VAMPOMI_OK) return die("sample subset");
     // every rank has joined the communicator (its init is collective): the
     // rendezvous file has served and must not be read by a later job
     if (rank == 0 && !rdzv_path.empty()) vio::rdzv_remove(rdzv_path);
@@ -304,7 +345,7 @@ int main(int argc, char** argv) {
     // as the reference does (src/vamp.cpp:396-401, rank 0): one step is one
     // iteration, and the host waits once per iteration, at its end
     auto t1 = std::chrono::steady_clock::now();
-    if (use_cov && vampomi_set_covariates(ctx, covs.data(), (int)opt.C, (int64_t)opt.N, 0) != VAMPOMI_OK)
+    if (use_cov && vampomi_set_covariates(ctx, covs.data(), (int)opt.C, n, subset ? 1 : 0) != VAMPOMI_OK)
         return die("covariates");
     if (vampomi_vamp_begin(ctx, &p, &r) != VAMPOMI_OK) return die("inference");
     if (use_cov) {  // src/vamp_probit.cpp:84-91, and the effects as a file

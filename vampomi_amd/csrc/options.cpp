@@ -70,6 +70,9 @@ bool parse(int argc, char** argv, Options& o, std::string& echo) {
         {"--batch-rhs", {Kind::Int, &o.batch_rhs, nullptr}},
         {"--meth-storage", {Kind::Str, &o.meth_storage, nullptr}},
         {"--meth-dtype", {Kind::Str, &o.meth_dtype, nullptr}},
+        {"--keep-file", {Kind::Str, &o.keep_file, nullptr}},
+        {"--keep-file-test", {Kind::Str, &o.keep_file_test, nullptr}},
+        {"--phen-na", {Kind::Str, &o.phen_na, nullptr}},
     };
     std::stringstream ss;
     ss << "\nardyh command line options:\n";
@@ -92,6 +95,11 @@ bool parse(int argc, char** argv, Options& o, std::string& echo) {
                 if ((name == "--meth-storage" || name == "--meth-dtype") && std::strcmp(val, "f64") != 0 &&
                     std::strcmp(val, "f32") != 0 && std::strcmp(val, "u16") != 0) {
                     std::cout << "FATAL  : option " << name << " has to be f64, f32 or u16! (" << val << " was passed)"
+                              << std::endl;
+                    return false;
+                }
+                if (name == "--phen-na" && std::strcmp(val, "fatal") != 0 && std::strcmp(val, "drop") != 0) {
+                    std::cout << "FATAL  : option --phen-na has to be fatal or drop! (" << val << " was passed)"
                               << std::endl;
                     return false;
                 }

@@ -30,6 +30,11 @@ struct Options {
     // (u16: 16-bit fixed point, k * 2^-16)
     std::string meth_storage = "f64", meth_dtype = "f64";
     bool meth_storage_set = false;  // --meth-storage was given (else the context's default stands)
+    // the samples of the files that the run keeps: --keep-file / --keep-file-test
+    // (PLINK --keep style, FID and IID per line; the latter for the test-mode
+    // trio) and --phen-na fatal | drop (an NA phenotype ends the job, the
+    // reference's behaviour, or drops its row).  --N / --N-test stay the files' rows
+    std::string keep_file, keep_file_test, phen_na = "fatal";
 };
 
 // Parses argv exactly like Options::read_command_line_options + check_options:
