@@ -1431,6 +1431,10 @@ double orc_t_sf(double t, double df) {
     if (isnan(t) || isnan(df)) return NAN;
     if (t <= 0.0) return t == 0.0 ? 0.5 : 1.0 - orc_t_sf(-t, df);
     const double a = 0.5 * df, b = 0.5, tt = t * t;
+    /* t = inf, or a finite t whose square overflows: x = df / (df + inf) = 0
+     * and I_0 = 0, which is what Boost returns (below, tt / (df + tt) would
+     * be inf / inf).  Every t with a finite square takes the path it took. */
+    if (!isfinite(tt)) return 0.0;
     const double lx = -log1p(tt / df);     /* ln x */
     const double l1x = log(tt / (df + tt)); /* ln (1 - x) */
     const double x = df / (df + tt);

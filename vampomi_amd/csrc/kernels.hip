@@ -3504,6 +3504,7 @@ __device__ double ibeta_cf(double a, double b, double x) {
 
 __device__ double t_sf_pos(double t, double df) {  // t > 0
     const double a = 0.5 * df, b = 0.5, tt = t * t;
+    if (!isfinite(tt)) return 0.0;  // t = inf or t * t overflows: x = 0, I_0 = 0 (as orc_t_sf)
     const double lx = -log1p(tt / df);
     const double l1x = log(tt / (df + tt));
     const double x = df / (df + tt);
