@@ -67,7 +67,8 @@ typedef enum {
     VAMPOMI_ERR_STATE = 6,        /* call out of order (e.g. Ax before data load) */
     VAMPOMI_ERR_OOM = 7,          /* device or host allocation failed */
     VAMPOMI_ERR_MODEL = 8,        /* unsupported --model (src/vamp.cpp:103-104) */
-    VAMPOMI_ERR_RANGE = 9         /* methylation values a VAMPOMI_STORE_U16 shard cannot hold */
+    VAMPOMI_ERR_RANGE = 9,        /* methylation values a VAMPOMI_STORE_U16 shard cannot hold */
+    VAMPOMI_ERR_NAN_METH = 10     /* missing methylation values (NaN) under VAMPOMI_NA_FATAL */
 } vampomi_status;
 
 /* where a caller buffer lives */
@@ -224,6 +225,49 @@ vampomi_status vampomi_load_meth_host_u16(vampomi_ctx* ctx, const uint16_t* X, i
  * Both are zero on F64 and F32 contexts and after a uint16 input.  Either
  * pointer may be NULL.  VAMPOMI_ERR_STATE before a shard is loaded. */
 vampomi_status vampomi_get_quant_stats(const vampomi_ctx* ctx, int64_t* clamped, double* max_abs_err);
+/* Missing methylation values.  A MISSING entry is a NaN of the input's element
+ * type (fp64 or fp32; any sign, any payload).  An infinity is a value.  uint16
+ * input has no missing code, and vampomi_generate_meth makes none: the policy
+ * does not touch them and their counts are zero.  With a row subset only the
+ * kept rows are looked at.  The policy is rank-local, as the storage is, and
+ * adds no collective.
+ *   VAMPOMI_NA_PASS (the default): nobody looks; a load does what it did before
+ *     the policy existed, launch for launch (a NaN loads silently into an F64 or
+ *     F32 shard and is VAMPOMI_ERR_RANGE on a U16 one).
+ *   VAMPOMI_NA_FATAL: a load that meets a missing entry fails with
+ *     VAMPOMI_ERR_NAN_METH; vampomi_last_error gives their number and the
+ *     smallest (global marker, the file's row), and the context is left without
+ *     a shard, as after VAMPOMI_ERR_RANGE.  On a U16 context a NaN gives this
+ *     error, an out-of-range value still VAMPOMI_ERR_RANGE, and both together
+ *     this error.
+ *   VAMPOMI_NA_MEAN: each missing entry of a marker is replaced by the mean
+ *     s / n_obs of the marker's observed entries, s their fp64 sum in a fixed
+ *     order that depends on the kept rows alone, and the mean
+ *     is stored as any input value is (as it is, rounded to nearest even, or
+ *     quantised).  A marker with no observed entry, or with
+ *     (double)n_missing > max_missing_frac * (double)N, is MASKED: every entry
+ *     is stored as 0, a constant column (mave 0, msig 1, exactly null).  Filled
+ *     and masked entries are not counted by vampomi_get_quant_stats; observed
+ *     ones are converted, range-checked and counted as ever.  Nothing after the
+ *     ingest knows of missingness: the context holds what vampomi_read_markers
+ *     returns and computes, bit for bit, what a plain context of the same
+ *     storage computes after loading that matrix.
+ * Under FATAL and MEAN every block of a load is staged on the device (also
+ * where the input's element type is the storage's) and one workgroup per
+ * column sweeps it twice.  max_missing_frac in [0, 1] matters under MEAN only.
+ * Legal only before the shard is allocated (VAMPOMI_ERR_STATE afterwards);
+ * another policy, or a fraction outside [0, 1] or NaN, is VAMPOMI_ERR_ARG. */
+#define VAMPOMI_NA_PASS 0
+#define VAMPOMI_NA_FATAL 1
+#define VAMPOMI_NA_MEAN 2
+vampomi_status vampomi_set_meth_na(vampomi_ctx* ctx, int policy, double max_missing_frac);
+vampomi_status vampomi_get_meth_na(const vampomi_ctx* ctx, int* policy, double* max_missing_frac);
+/* What the last load saw (this rank's shard): the missing entries, the markers
+ * that had any, the markers masked, and per_marker (M entries, host; the true
+ * count of a masked marker too).  Any pointer may be NULL.  All zeros under
+ * VAMPOMI_NA_PASS.  VAMPOMI_ERR_STATE before a shard is loaded. */
+vampomi_status vampomi_get_missing_stats(const vampomi_ctx* ctx, int64_t* missing, int64_t* markers_with_missing,
+                                         int64_t* markers_masked, int64_t* per_marker);
 /* synthetic shard generated on the device (bit-identical to the oracle's; an
  * F32 context stores the generator's value rounded: VAMPOMI_GEN_GAUSS values
  * are exactly floats, VAMPOMI_GEN_METH values are not; a U16 context stores

@@ -20,13 +20,15 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import (CLI_PATH, GEN_GAUSS, GEN_METH, LIB_PATH, MAX_L, MEM_DEVICE, MEM_HOST, STORE_F32, STORE_F64,
-                   STORE_U16, UNIQUE_ID_BYTES, Params, Result, ShardDesc, Stats, VampomiError, check, load)
+from ._lib import (CLI_PATH, GEN_GAUSS, GEN_METH, LIB_PATH, MAX_L, MEM_DEVICE, MEM_HOST, NA_FATAL, NA_MEAN, NA_PASS,
+                   STORE_F32, STORE_F64, STORE_U16, UNIQUE_ID_BYTES, Params, Result, ShardDesc, Stats, VampomiError,
+                   check, load)
 
 __all__ = ["Data", "Vamp", "VampOptions", "divide_work", "comm_unique_id", "phen_rows", "VampomiError", "LIB_PATH", "CLI_PATH",
            "GEN_GAUSS", "GEN_METH", "STORE_F64", "STORE_F32", "STORE_U16", "load"]
 
 _STORAGE = {"f64": STORE_F64, "f32": STORE_F32, "u16": STORE_U16}
+_METH_NA = {"pass": NA_PASS, "fatal": NA_FATAL, "mean": NA_MEAN}
 
 
 def _dp(a: np.ndarray):
@@ -93,13 +95,29 @@ class Data:
     keep those rows; the context then holds, bit for bit, what a plain one
     holds after loading files with the other rows removed.  :meth:`set_phen`
     and :meth:`set_covariates` keep taking ``d.N`` rows.
+
+    ``meth_na``: what a load does with a missing methylation value, a NaN of
+    fp64 or fp32 input (uint16 input has none).  ``"pass"`` (the default):
+    nothing, as ever.  ``"fatal"``: the load raises ``VampomiError`` (status 10,
+    ``ERR_NAN_METH``; the message gives their number and the first marker and
+    row).  ``"mean"``: each is replaced by the mean of the marker's observed
+    entries among the kept rows, stored as any input value is; a marker with no
+    observed entry, or with more than ``max_missing_frac`` of its entries
+    missing, is stored as zeros, a constant column that the model sees as
+    exactly null.  Everything after the load treats the filled matrix
+    (:meth:`get_meth_data`) as the data.  :meth:`missing_stats` and
+    :meth:`missing_counts` tell what the last load found.
     """
 
     def __init__(self, N: int, Mt: int, rank: int = 0, nranks: int = 1, comm_id: Optional[bytes] = None,
                  device: int = -1, alpha_scale: float = 1.0, storage: Optional[str] = None,
-                 rows: Optional[Sequence[int]] = None):
+                 rows: Optional[Sequence[int]] = None, meth_na: Optional[str] = None, max_missing_frac: float = 1.0):
         if storage is not None and storage not in _STORAGE:
             raise ValueError(f'storage must be "f64", "f32" or "u16", not {storage!r}')
+        if meth_na is not None and meth_na not in _METH_NA:
+            raise ValueError(f'meth_na must be "pass", "fatal" or "mean", not {meth_na!r}')
+        if max_missing_frac != 1.0 and meth_na != "mean":
+            raise ValueError('max_missing_frac needs meth_na="mean"')
         self.N_file, self.rows = N, None
         if rows is not None:
             self.rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
@@ -124,6 +142,35 @@ class Data:
             check(self._lib.vampomi_set_storage(self.ctx, _STORAGE[storage]))
         if self.rows is not None:
             check(self._lib.vampomi_set_row_subset(self.ctx, self.N_file, _dp(self.rows), len(self.rows)))
+        if meth_na is not None:
+            check(self._lib.vampomi_set_meth_na(self.ctx, _METH_NA[meth_na], max_missing_frac))
+
+    @property
+    def meth_na(self) -> str:
+        p, f = C.c_int(), C.c_double()
+        check(self._lib.vampomi_get_meth_na(self.ctx, C.byref(p), C.byref(f)))
+        return {NA_FATAL: "fatal", NA_MEAN: "mean"}.get(p.value, "pass")
+
+    @property
+    def max_missing_frac(self) -> float:
+        p, f = C.c_int(), C.c_double()
+        check(self._lib.vampomi_get_meth_na(self.ctx, C.byref(p), C.byref(f)))
+        return f.value
+
+    def missing_stats(self) -> dict:
+        """What the last load found in this shard: ``missing`` entries (NaN, among
+        the kept rows), ``markers_with_missing``, and ``markers_masked`` (stored
+        as zeros under ``"mean"``).  Zeros under ``"pass"``, which does not look."""
+        a, b, m = C.c_int64(), C.c_int64(), C.c_int64()
+        check(self._lib.vampomi_get_missing_stats(self.ctx, C.byref(a), C.byref(b), C.byref(m), None))
+        return {"missing": a.value, "markers_with_missing": b.value, "markers_masked": m.value}
+
+    def missing_counts(self) -> np.ndarray:
+        """The missing entries of each local marker (int64, M; a masked marker's
+        true count)."""
+        out = np.zeros(max(self.M, 1), dtype=np.int64)
+        check(self._lib.vampomi_get_missing_stats(self.ctx, None, None, None, _dp(out)))
+        return out[: self.M]
 
     @property
     def storage(self) -> str:

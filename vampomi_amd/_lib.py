@@ -29,11 +29,12 @@ UNIQUE_ID_BYTES = 128
 MEM_HOST, MEM_DEVICE = 0, 1
 GEN_GAUSS, GEN_METH = 0, 1
 STORE_F64, STORE_F32, STORE_U16 = 0, 1, 16
+NA_PASS, NA_FATAL, NA_MEAN = 0, 1, 2
 
 STATUS = {
     0: "OK", 1: "ERR_ARG", 2: "ERR_HIP", 3: "ERR_RCCL", 4: "ERR_IO",
     5: "ERR_NAN_PHEN", 6: "ERR_STATE", 7: "ERR_OOM", 8: "ERR_MODEL",
-    9: "ERR_RANGE",
+    9: "ERR_RANGE", 10: "ERR_NAN_METH",
 }
 
 
@@ -121,6 +122,9 @@ SIGNATURES = {
     "vampomi_load_meth_file_u16": (C.c_int, [_P, C.c_char_p]),
     "vampomi_load_meth_host_u16": (C.c_int, [_P, _P, C.c_int64]),
     "vampomi_get_quant_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "vampomi_set_meth_na": (C.c_int, [_P, C.c_int, C.c_double]),
+    "vampomi_get_meth_na": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "vampomi_get_missing_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
     "vampomi_generate_meth": (C.c_int, [_P, C.c_uint64, C.c_int]),
     "vampomi_read_phen": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "vampomi_set_phen": (C.c_int, [_P, _P, C.c_int]),

@@ -102,6 +102,15 @@ struct vampomi_ctx {
     vk::QuantRec* qrec = nullptr;
     int64_t q_clamped = 0;
     double q_max_err = 0.0;
+    // missing values (vampomi_set_meth_na; fixed once X is allocated, rank-local):
+    // the policy, what the last load's vk::na_ingest_cols saw (na_rec; na_cnt: M
+    // per-marker counts) and the host copy (vampomi_get_missing_stats)
+    int na_policy = VAMPOMI_NA_PASS;
+    double na_max_frac = 1.0;
+    vk::NaRec* na_rec = nullptr;
+    int64_t* na_cnt = nullptr;
+    int64_t na_missing = 0, na_markers = 0, na_masked = 0;
+    std::vector<int64_t> na_per_marker;  // empty: all zeros
     // the row subset (vampomi_set_row_subset; N_file == 0: none): the files hold
     // N_file rows of which rows_host (N ascending indices) are loaded; rows_dev:
     // their device copy for vk::gather_cols

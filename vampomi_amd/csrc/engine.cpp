@@ -1131,6 +1131,10 @@ void release_ctx_resources(vampomi_ctx* c) {
     c->qrec = nullptr;
     if (c->rows_dev) (void)hipFree(c->rows_dev);
     c->rows_dev = nullptr;
+    if (c->na_rec) (void)hipFree(c->na_rec);
+    c->na_rec = nullptr;
+    if (c->na_cnt) (void)hipFree(c->na_cnt);
+    c->na_cnt = nullptr;
     for (double** p : {&c->mave, &c->msig, &c->y, &c->ax_part, &c->red_part, &c->scal, &c->nbuf, &c->mbuf,
                        &c->op_part, &c->op_nvec, &c->cov_Z, &c->cov_part, &c->cov_dev})
         dev_free(*p);
@@ -1328,6 +1332,25 @@ extern "C" vampomi_status vampomi_get_storage(const vampomi_ctx* c, int* storage
     return VAMPOMI_OK;
 }
 
+extern "C" vampomi_status vampomi_set_meth_na(vampomi_ctx* c, int policy, double max_missing_frac) {
+    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
+    if (policy != VAMPOMI_NA_PASS && policy != VAMPOMI_NA_FATAL && policy != VAMPOMI_NA_MEAN)
+        return fail(VAMPOMI_ERR_ARG, "the policy must be VAMPOMI_NA_PASS, VAMPOMI_NA_FATAL or VAMPOMI_NA_MEAN");
+    if (!(max_missing_frac >= 0.0 && max_missing_frac <= 1.0))
+        return fail(VAMPOMI_ERR_ARG, "max_missing_frac must lie in [0, 1]");
+    if (c->X) return fail(VAMPOMI_ERR_STATE, "the NaN policy is fixed once the methylation shard is allocated");
+    c->na_policy = policy;
+    c->na_max_frac = max_missing_frac;
+    return VAMPOMI_OK;
+}
+
+extern "C" vampomi_status vampomi_get_meth_na(const vampomi_ctx* c, int* policy, double* max_missing_frac) {
+    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
+    if (policy) *policy = c->na_policy;
+    if (max_missing_frac) *max_missing_frac = c->na_max_frac;
+    return VAMPOMI_OK;
+}
+
 extern "C" vampomi_status vampomi_set_row_subset(vampomi_ctx* c, int64_t N_file, const int64_t* rows, int64_t n) {
     if (!c || !rows) return fail(VAMPOMI_ERR_ARG, "null argument");
     if (c->X) return fail(VAMPOMI_ERR_STATE, "the row subset is fixed once the methylation shard is allocated");
@@ -1423,6 +1446,69 @@ static vampomi_status quant_end(vampomi_ctx* c) {
     return VAMPOMI_OK;
 }
 
+// whether a load of elements of in_es bytes looks for missing values: a policy
+// other than pass, and an input that can hold a NaN
+static bool na_active(const vampomi_ctx* c, int in_es) { return c->na_policy != VAMPOMI_NA_PASS && in_es != 2; }
+
+// A load starts with the missing-value counts forgotten and, where it will
+// look (look: na_active), the device record and the per-marker counters zeroed
+static vampomi_status na_begin(vampomi_ctx* c, bool look) {
+    c->na_missing = c->na_markers = c->na_masked = 0;
+    c->na_per_marker.clear();
+    if (!look) return VAMPOMI_OK;
+    const size_t cb = (size_t)std::max<int64_t>(c->M, 1) * sizeof(int64_t);
+    if ((!c->na_rec && hipMalloc((void**)&c->na_rec, sizeof(vk::NaRec)) != hipSuccess) ||
+        (!c->na_cnt && hipMalloc((void**)&c->na_cnt, cb) != hipSuccess)) {
+        (void)hipGetLastError();
+        return fail(VAMPOMI_ERR_OOM, "missing-value counters");
+    }
+    HIPCHK(hipMemsetAsync(c->na_rec, 0, sizeof(vk::NaRec), c->st));
+    HIPCHK(hipMemsetAsync(&c->na_rec->first, 0xff, sizeof(unsigned long long), c->st));
+    HIPCHK(hipMemsetAsync(c->na_cnt, 0, cb, c->st));
+    return VAMPOMI_OK;
+}
+
+// ... and ends with the record read (before quant_end: of a NaN and a value
+// out of range the NaN is reported): under VAMPOMI_NA_FATAL missing entries
+// fail the load with VAMPOMI_ERR_NAN_METH and leave the context without X
+static vampomi_status na_end(vampomi_ctx* c, bool look) {
+    if (!look) return VAMPOMI_OK;
+    vk::NaRec r{};
+    HIPCHK(hipMemcpyAsync(&r, c->na_rec, sizeof r, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    if (r.missing && c->na_policy == VAMPOMI_NA_FATAL) {
+        c->have_X = false;
+        const long long marker = (long long)(r.first / (unsigned long long)rows_in(c));
+        const long long row = (long long)(r.first % (unsigned long long)rows_in(c));  // (the file's row)
+        return fail(VAMPOMI_ERR_NAN_METH, std::to_string(r.missing) + " missing methylation value(s) (NaN); the first "
+                                          "is marker " + std::to_string(marker) + ", row " + std::to_string(row));
+    }
+    if (r.missing) {
+        c->na_per_marker.resize((size_t)c->M);
+        HIPCHK(hipMemcpyAsync(c->na_per_marker.data(), c->na_cnt, (size_t)c->M * sizeof(int64_t),
+                              hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+    }
+    c->na_missing = (int64_t)r.missing;
+    c->na_markers = (int64_t)r.markers;
+    c->na_masked = (int64_t)r.masked;
+    return VAMPOMI_OK;
+}
+
+extern "C" vampomi_status vampomi_get_missing_stats(const vampomi_ctx* c, int64_t* missing,
+                                                    int64_t* markers_with_missing, int64_t* markers_masked,
+                                                    int64_t* per_marker) {
+    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
+    if (!c->have_X) return fail(VAMPOMI_ERR_STATE, "no methylation data loaded");
+    if (missing) *missing = c->na_missing;
+    if (markers_with_missing) *markers_with_missing = c->na_markers;
+    if (markers_masked) *markers_masked = c->na_masked;
+    if (per_marker && c->na_per_marker.empty()) std::fill(per_marker, per_marker + c->M, (int64_t)0);
+    if (per_marker && !c->na_per_marker.empty())
+        std::copy(c->na_per_marker.begin(), c->na_per_marker.end(), per_marker);
+    return VAMPOMI_OK;
+}
+
 extern "C" vampomi_status vampomi_get_quant_stats(const vampomi_ctx* c, int64_t* clamped, double* max_abs_err) {
     if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
     if (!c->have_X) return fail(VAMPOMI_ERR_STATE, "no methylation data loaded");
@@ -1442,13 +1528,15 @@ extern "C" vampomi_status vampomi_get_quant_stats(const vampomi_ctx* c, int64_t*
 // on the context's stream, so the caller may reuse src once the stream has
 // passed this point.  With a row subset the block's columns hold N_file
 // elements and every block takes the staging hop: vk::gather_cols keeps the
-// subset's rows as it converts (or copies).
+// subset's rows as it converts (or copies).  Under a NaN policy other than
+// pass every block of doubles or floats takes the staging hop too, and
+// vk::na_ingest_cols does the conversion, the gather and the policy's work.
 static vampomi_status put_cols(vampomi_ctx* c, int64_t i0, int64_t nc, const void* src, int64_t ld_in, int in_es,
                                void** stage, size_t* cap_bytes) {
     if (nc <= 0) return VAMPOMI_OK;
     const size_t es = (size_t)c->esize();
     char* dst = (char*)c->X + (size_t)i0 * (size_t)c->ld * es;
-    if ((size_t)in_es == es && !c->N_file) {
+    if ((size_t)in_es == es && !c->N_file && !na_active(c, in_es)) {
         HIPCHK(hipMemcpy2DAsync(dst, (size_t)c->ld * es, src, (size_t)ld_in * es, (size_t)c->N * es, (size_t)nc,
                                 hipMemcpyHostToDevice, c->st));
         return VAMPOMI_OK;
@@ -1468,7 +1556,11 @@ static vampomi_status put_cols(vampomi_ctx* c, int64_t i0, int64_t nc, const voi
     }
     HIPCHK(hipMemcpy2DAsync(*stage, (size_t)Nin * in_es, src, (size_t)ld_in * in_es, (size_t)Nin * in_es,
                             (size_t)nc, hipMemcpyHostToDevice, c->st));
-    if (c->N_file)
+    if (na_active(c, in_es))
+        HIPCHK(vk::na_ingest_cols(*stage, in_es == 4 ? vk::kXF32 : vk::kXF64, Nin, c->rows_dev, c->N, nc, dst, c->ek(),
+                                  c->ld, Nin, c->S + i0, c->na_policy, c->na_max_frac, c->na_cnt + i0, c->na_rec,
+                                  c->qrec, c->st));
+    else if (c->N_file)
         HIPCHK(vk::gather_cols(*stage, in_es == 2 ? vk::kXU16 : in_es == 4 ? vk::kXF32 : vk::kXF64, Nin, c->rows_dev,
                                c->N, nc, dst, c->ek(), c->ld, Nin, c->S + i0, c->qrec, c->st));
     else if (es == 2 && in_es == 8)
@@ -1496,10 +1588,12 @@ static vampomi_status load_host(vampomi_ctx* c, const void* X, int64_t ld_in, in
     HIPCHK(hipSetDevice(c->device));
     STCHK(ensure_X(c));
     STCHK(quant_begin(c));
+    const bool look = na_active(c, in_es);
+    STCHK(na_begin(c, look));
     void* stage = nullptr;
     size_t cap = 0;
     vampomi_status st = VAMPOMI_OK;
-    const int64_t chunk = (int64_t)in_es == c->esize() && !c->N_file
+    const int64_t chunk = (int64_t)in_es == c->esize() && !c->N_file && !look
                               ? std::max<int64_t>(c->M, 1)
                               : std::max<int64_t>(1, io_chunk_bytes() / (rows_in(c) * in_es));
     for (int64_t i0 = 0; i0 < c->M && st == VAMPOMI_OK; i0 += chunk)
@@ -1510,6 +1604,7 @@ static vampomi_status load_host(vampomi_ctx* c, const void* X, int64_t ld_in, in
         (void)hipFree(stage);
     }
     if (st != VAMPOMI_OK) return st;
+    STCHK(na_end(c, look));
     STCHK(quant_end(c));
     return finish_X(c);
 }
@@ -1576,6 +1671,11 @@ static vampomi_status load_file(vampomi_ctx* c, const char* path, int in_es) {
         ::close(fd);
         return s0;
     }
+    const bool look = na_active(c, in_es);
+    if (const vampomi_status s0 = na_begin(c, look)) {
+        ::close(fd);
+        return s0;
+    }
     const size_t colb = (size_t)rows_in(c) * (size_t)in_es;
     const size_t chunk_cols = std::max<size_t>(1, (size_t)io_chunk_bytes() / colb);
     const char* env = std::getenv("VAMPOMI_IO_THREADS");
@@ -1624,6 +1724,7 @@ static vampomi_status load_file(vampomi_ctx* c, const char* path, int in_es) {
     if (stage) (void)hipFree(stage);
     ::close(fd);
     if (st != VAMPOMI_OK) return st;
+    STCHK(na_end(c, look));
     STCHK(quant_end(c));
     return finish_X(c);
 }
@@ -1647,6 +1748,7 @@ extern "C" vampomi_status vampomi_generate_meth(vampomi_ctx* c, uint64_t seed, i
     HIPCHK(hipSetDevice(c->device));
     STCHK(ensure_X(c));
     STCHK(quant_begin(c));
+    STCHK(na_begin(c, false));
     if (!c->u16()) {
         HIPCHK(vk::gen_markers(seed, kind, c->N, c->ld, c->S, c->M, c->X, c->ek(), c->st));
         return finish_X(c);

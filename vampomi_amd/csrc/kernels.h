@@ -331,6 +331,36 @@ hipError_t dequant_cols(const uint16_t* src, int64_t lds, int64_t N, int64_t nco
 hipError_t gather_cols(const void* src, int src_ek, int64_t lds, const int32_t* rows, int64_t n, int64_t ncols,
                        void* dst, int dst_ek, int64_t ldd, int64_t nfile, int64_t col0, QuantRec* rec,
                        hipStream_t st);
+// ---- missing values (NaN): the column-wise ingest ----------------------------
+// What na_ingest_cols has seen since the record was zeroed (first: all ones):
+// integer sums and a minimum, so none depends on the order anything ran in.
+struct NaRec {
+    unsigned long long missing;  // NaN entries among the kept rows
+    unsigned long long first;    // the smallest index (col0 + c) * nfile + row of one (~0: none)
+    unsigned long long markers;  // columns with at least one
+    unsigned long long masked;   // columns stored as zeros (kNaMean)
+};
+enum { kNaFatal = 1, kNaMean = 2 };  // (VAMPOMI_NA_FATAL / VAMPOMI_NA_MEAN)
+// The ingest conversions (narrow_cols, widen_cols, quantise_cols, gather_cols;
+// a copy where the kinds agree) of a staged chunk of doubles or floats
+// (src_ek kXF64 / kXF32) with a NaN policy.  rows == nullptr: the n = nfile
+// rows of a column as they are; else the n ascending device indices of the
+// kept rows, as gather_cols takes them.  One workgroup per column, two sweeps:
+//   1. the NaNs among the kept rows are counted (cnt[c], and *nrec) and the
+//      other kept entries summed in fp64: thread t adds rows t, t + 256, ...
+//      in that order, each wave's 64 sums are folded by wave_sum's butterfly,
+//      and the four wave sums added in wave order.  The order depends on n and
+//      on which rows are NaN, on nothing else.
+//   2. kNaMean: each kept entry is stored as conv(x), a NaN as conv(s / n_obs);
+//      a column with n_obs == 0 or (double)n_missing > max_frac * (double)n is
+//      stored as zeros.  Into kXU16 the observed entries (a masked column's
+//      too) go through *qrec as in quantise_cols; the fill and the zeros do not.
+//      kNaFatal: the same for a column without NaN; a column with one is not
+//      stored (the load fails).
+// cnt: ncols device counters (the chunk's slice of the shard's)
+hipError_t na_ingest_cols(const void* src, int src_ek, int64_t lds, const int32_t* rows, int64_t n, int64_t ncols,
+                          void* dst, int dst_ek, int64_t ldd, int64_t nfile, int64_t col0, int mode, double max_frac,
+                          int64_t* cnt, NaRec* nrec, QuantRec* qrec, hipStream_t st);
 // beta_i = gauss(seed) for causal markers (uniform < lam), else 0; the count
 // of causal markers in ro.out[0]
 hipError_t gen_beta(uint64_t seed, double lam, int64_t S, int64_t M, double* beta, const RedOut& ro, hipStream_t st);

@@ -1822,6 +1822,178 @@ hipError_t gather_cols(const void* src, int src_ek, int64_t lds, const int32_t* 
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// missing values (NaN): the ingest conversions, column by column
+// ---------------------------------------------------------------------------
+// what the ingest stores for the value v where no record is kept: the fill of
+// a missing entry (QuantAcc::put's k for a v in [0, 1], uncounted; 0 for any
+// other, which only an infinite observed entry can make of a mean)
+template <class XD>
+__device__ __forceinline__ XD na_store(double v) {
+    return (XD)v;
+}
+template <>
+__device__ __forceinline__ uint16_t na_store<uint16_t>(double v) {
+    if (!(v >= 0.0 && v <= 1.0)) return 0;
+    const double r = __builtin_rint(v * 65536.0);
+    return (uint16_t)(r > 65535.0 ? 65535u : (unsigned)r);
+}
+
+// the loads a thread issues before it uses the first (a 256 MB chunk of long
+// columns is a few hundred workgroups, about one per CU: the memory-level
+// parallelism has to come from within the thread).  The values are then used
+// in row order, so the depth does not change a sum
+static constexpr int kNaDepth = 8;
+
+// One workgroup per column (grid-stride over the chunk's columns), two sweeps
+// (kernels.h); the second re-reads what this workgroup has just read, out of
+// L2.  The source columns are packed, so a column starts only as aligned as
+// its element: one element per load, as in gather_kernel.  GATHER: row j of
+// the output is row rows[j] of the input.
+template <class XS, class XD, bool GATHER>
+__global__ __launch_bounds__(kBlock) void na_ingest_kernel(const XS* __restrict__ src, int64_t lds,
+                                                           const int32_t* __restrict__ rows, int64_t n, int64_t ncols,
+                                                           XD* __restrict__ dst, int64_t ldd, int64_t nfile,
+                                                           int64_t col0, int mode, double max_frac,
+                                                           int64_t* __restrict__ cnt, NaRec* __restrict__ nrec,
+                                                           QuantRec* __restrict__ qrec) {
+    __shared__ double l_sum[4];
+    __shared__ unsigned long long l_cnt[4], l_first[4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    QuantAcc acc;
+    for (int64_t c = blockIdx.x; c < ncols; c += gridDim.x) {
+        const XS* __restrict__ col = src + c * lds;
+        // sweep 1: this thread's rows in ascending order
+        double s = 0.0;
+        unsigned long long miss = 0, first = ~0ull;
+        const auto see = [&](XS xs, int64_t r) {
+            const double x = (double)xs;
+            if (__builtin_isnan(x)) {
+                ++miss;
+                const unsigned long long at = (unsigned long long)((col0 + c) * nfile + r);
+                first = at < first ? at : first;
+            } else {
+                s += x;
+            }
+        };
+        int64_t j = threadIdx.x;
+        for (; j + (kNaDepth - 1) * kBlock < n; j += kNaDepth * kBlock) {  // kNaDepth loads in flight, then in order
+            XS x[kNaDepth];
+            int64_t r[kNaDepth];
+#pragma unroll
+            for (int u = 0; u < kNaDepth; ++u) {
+                r[u] = GATHER ? (int64_t)rows[j + u * kBlock] : j + u * kBlock;
+                x[u] = col[r[u]];
+            }
+#pragma unroll
+            for (int u = 0; u < kNaDepth; ++u) see(x[u], r[u]);
+        }
+        for (; j < n; j += kBlock) {
+            const int64_t r = GATHER ? (int64_t)rows[j] : j;
+            see(col[r], r);
+        }
+        s = wave_sum(s);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            miss += __shfl_xor(miss, o, 64);
+            const unsigned long long f = __shfl_xor(first, o, 64);
+            first = f < first ? f : first;
+        }
+        __syncthreads();  // the previous column's totals have been read
+        if (lane == 0) {
+            l_sum[w] = s;
+            l_cnt[w] = miss;
+            l_first[w] = first;
+        }
+        __syncthreads();
+        s = ((l_sum[0] + l_sum[1]) + l_sum[2]) + l_sum[3];
+        miss = l_cnt[0] + l_cnt[1] + l_cnt[2] + l_cnt[3];
+        const bool masked = mode == kNaMean && (miss == (unsigned long long)n || (double)miss > max_frac * (double)n);
+        if (threadIdx.x == 0) {
+            cnt[c] = (int64_t)miss;
+            if (miss) {
+                unsigned long long f = l_first[0];
+#pragma unroll
+                for (int k = 1; k < 4; ++k) f = l_first[k] < f ? l_first[k] : f;
+                atomicAdd(&nrec->missing, miss);
+                atomicMin(&nrec->first, f);
+                atomicAdd(&nrec->markers, 1ull);
+                if (masked) atomicAdd(&nrec->masked, 1ull);
+            }
+        }
+        if (mode == kNaFatal && miss) continue;  // (block-uniform) the load fails: nothing to store
+        // sweep 2
+        const double fill = masked ? 0.0 : s / (double)((unsigned long long)n - miss);
+        const XD fill_st = na_store<XD>(fill);
+        XD* __restrict__ out = dst + c * ldd;
+        const auto put = [&](XS x, int64_t r) -> XD {
+            XD v = fill_st;
+            if (!__builtin_isnan(x)) {
+                if constexpr (sizeof(XD) == 2)
+                    v = acc.put((double)x, (unsigned long long)((col0 + c) * nfile + r));
+                else
+                    v = (XD)x;
+                if (masked) v = (XD)0;
+            }
+            return v;
+        };
+        for (j = threadIdx.x; j + (kNaDepth - 1) * kBlock < n; j += kNaDepth * kBlock) {
+            XS x[kNaDepth];
+            int64_t r[kNaDepth];
+#pragma unroll
+            for (int u = 0; u < kNaDepth; ++u) {
+                r[u] = GATHER ? (int64_t)rows[j + u * kBlock] : j + u * kBlock;
+                x[u] = col[r[u]];
+            }
+#pragma unroll
+            for (int u = 0; u < kNaDepth; ++u) out[j + u * kBlock] = put(x[u], r[u]);
+        }
+        for (; j < n; j += kBlock) {
+            const int64_t r = GATHER ? (int64_t)rows[j] : j;
+            out[j] = put(col[r], r);
+        }
+    }
+    if constexpr (sizeof(XD) == 2) acc.flush(qrec);
+}
+
+template <class XS, class XD>
+static void na_launch(const void* src, int64_t lds, const int32_t* rows, int64_t n, int64_t ncols, void* dst,
+                      int64_t ldd, int64_t nfile, int64_t col0, int mode, double max_frac, int64_t* cnt, NaRec* nrec,
+                      QuantRec* qrec, hipStream_t st) {
+    const dim3 grid((unsigned)std::min<int64_t>(ncols, 65536));
+    if (rows)
+        hipLaunchKernelGGL((na_ingest_kernel<XS, XD, true>), grid, dim3(kBlock), 0, st, static_cast<const XS*>(src),
+                           lds, rows, n, ncols, static_cast<XD*>(dst), ldd, nfile, col0, mode, max_frac, cnt, nrec,
+                           qrec);
+    else
+        hipLaunchKernelGGL((na_ingest_kernel<XS, XD, false>), grid, dim3(kBlock), 0, st, static_cast<const XS*>(src),
+                           lds, rows, n, ncols, static_cast<XD*>(dst), ldd, nfile, col0, mode, max_frac, cnt, nrec,
+                           qrec);
+}
+
+hipError_t na_ingest_cols(const void* src, int src_ek, int64_t lds, const int32_t* rows, int64_t n, int64_t ncols,
+                          void* dst, int dst_ek, int64_t ldd, int64_t nfile, int64_t col0, int mode, double max_frac,
+                          int64_t* cnt, NaRec* nrec, QuantRec* qrec, hipStream_t st) {
+    if (n <= 0 || ncols <= 0) return hipSuccess;
+    if (!cnt || !nrec || n > nfile || (!rows && n != nfile) || lds < nfile || ldd < n ||
+        (mode != kNaFatal && mode != kNaMean) || (src_ek != kXF64 && src_ek != kXF32) || (dst_ek == kXU16 && !qrec))
+        return hipErrorInvalidValue;
+    auto go = [&](auto xs, auto xd) {
+        na_launch<decltype(xs), decltype(xd)>(src, lds, rows, n, ncols, dst, ldd, nfile, col0, mode, max_frac, cnt,
+                                              nrec, qrec, st);
+    };
+    const bool d = src_ek == kXF64;
+    if (dst_ek == kXF64)
+        d ? go(double{}, double{}) : go(float{}, double{});
+    else if (dst_ek == kXF32)
+        d ? go(double{}, float{}) : go(float{}, float{});
+    else if (dst_ek == kXU16)
+        d ? go(double{}, uint16_t{}) : go(float{}, uint16_t{});
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
 __global__ __launch_bounds__(kBlock) void gen_beta_kernel(uint64_t seed, double lam, int64_t S, int64_t M,
                                                           double* beta, RedOut ro) {
     __shared__ double lds[4];

@@ -257,6 +257,11 @@ int main(int argc, char** argv) {
                                                              : VAMPOMI_STORE_F64) != VAMPOMI_OK)
         return die("methylation storage");
     if (subset && vampomi_set_row_subset(ctx, N_file, rows.data(), n) != VAMPOMI_OK) return die("sample subset");
+    // (without the flag no call: the load is what it was)
+    if (opt.meth_na != "pass" &&
+        vampomi_set_meth_na(ctx, opt.meth_na == "mean" ? VAMPOMI_NA_MEAN : VAMPOMI_NA_FATAL, opt.meth_na_max_frac) !=
+            VAMPOMI_OK)
+        return die("missing-value policy");
     // every rank has joined the communicator (its init is collective): the
     // rendezvous file has served and must not be read by a later job
     if (rank == 0 && !rdzv_path.empty()) vio::rdzv_remove(rdzv_path);
@@ -273,6 +278,14 @@ int main(int argc, char** argv) {
          : opt.meth_dtype == "f32" ? vampomi_load_meth_file_f32(ctx, meth.c_str())
                                    : vampomi_load_meth_file(ctx, meth.c_str())) != VAMPOMI_OK)
         return die("methylation data");
+    {  // what --meth-na mean found in this rank's shard
+        int64_t missing = 0, with = 0, masked = 0;
+        if (vampomi_get_missing_stats(ctx, &missing, &with, &masked, nullptr) != VAMPOMI_OK)
+            return die("missing-value counts");
+        if (missing)
+            std::printf("INFO   : markers [%lld, %lld): %lld missing values in %lld markers, %lld masked\n",
+                        (long long)S, (long long)(S + M), (long long)missing, (long long)with, (long long)masked);
+    }
     // the ranks' shards load at their own pace (one rank's file may come off
     // slower storage): they meet here under a limit of their own, so the
     // first collective of the run is not the one that waits for the slowest

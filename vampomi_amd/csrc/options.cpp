@@ -73,6 +73,8 @@ bool parse(int argc, char** argv, Options& o, std::string& echo) {
         {"--keep-file", {Kind::Str, &o.keep_file, nullptr}},
         {"--keep-file-test", {Kind::Str, &o.keep_file_test, nullptr}},
         {"--phen-na", {Kind::Str, &o.phen_na, nullptr}},
+        {"--meth-na", {Kind::Str, &o.meth_na, nullptr}},
+        {"--meth-na-max-frac", {Kind::Str, nullptr, nullptr}},
     };
     std::stringstream ss;
     ss << "\nardyh command line options:\n";
@@ -103,10 +105,27 @@ bool parse(int argc, char** argv, Options& o, std::string& echo) {
                               << std::endl;
                     return false;
                 }
+                if (name == "--meth-na" && std::strcmp(val, "pass") != 0 && std::strcmp(val, "fatal") != 0 &&
+                    std::strcmp(val, "mean") != 0) {
+                    std::cout << "FATAL  : option --meth-na has to be pass, fatal or mean! (" << val << " was passed)"
+                              << std::endl;
+                    return false;
+                }
+                if (name == "--meth-na-max-frac") {
+                    char* end = nullptr;
+                    const double f = std::strtod(val, &end);
+                    if (end == val || *end != '\0' || !(f >= 0.0 && f <= 1.0)) {
+                        std::cout << "FATAL  : option --meth-na-max-frac has to be a number in [0, 1]! (" << val
+                                  << " was passed)" << std::endl;
+                        return false;
+                    }
+                    o.meth_na_max_frac = f;
+                    o.meth_na_max_frac_set = true;
+                }
                 if (name == "--meth-storage") o.meth_storage_set = true;
                 if (name == "--seed")
                     o.seed = std::strtoull(val, nullptr, 0);
-                else
+                else if (fl.dst)
                     *static_cast<std::string*>(fl.dst) = val;
                 ss << name << " " << val << "\n";
                 break;
@@ -156,6 +175,11 @@ bool parse(int argc, char** argv, Options& o, std::string& echo) {
         }
     }
     echo = ss.str();
+    if (o.meth_na_max_frac_set && o.meth_na != "mean") {
+        std::cout << "FATAL  : option --meth-na-max-frac needs --meth-na mean! (--meth-na is " << o.meth_na << ")"
+                  << std::endl;
+        return false;
+    }
     if (o.meth_file.empty() && o.meth_file_test.empty()) {  // check_options (:299-303)
         std::cout << "FATAL  : no meth file provided! Please use the --meth-file option." << std::endl;
         return false;

@@ -35,6 +35,13 @@ struct Options {
     // trio) and --phen-na fatal | drop (an NA phenotype ends the job, the
     // reference's behaviour, or drops its row).  --N / --N-test stay the files' rows
     std::string keep_file, keep_file_test, phen_na = "fatal";
+    // missing methylation values (NaN) in --meth-file / --meth-file-test:
+    // --meth-na pass | fatal | mean (nobody looks; the load fails; the marker's
+    // mean is stored) and, with mean, --meth-na-max-frac F in [0, 1]: a marker
+    // with more than F of its entries missing is stored as zeros
+    std::string meth_na = "pass";
+    double meth_na_max_frac = 1.0;
+    bool meth_na_max_frac_set = false;
 };
 
 // Parses argv exactly like Options::read_command_line_options + check_options:
