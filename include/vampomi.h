@@ -33,6 +33,8 @@
  *   run mode test              src/main_meth.cpp:112-205 -> vampomi_test_metrics (COLLECTIVE)
  *   association_test loo / se  src/main_meth.cpp:206-264, src/data.cpp:385-417,
  *                              src/utilities.cpp:269-282 -> vampomi_assoc_loo / _se
+ *   (not in the reference) covariates regressed out of the linear model's
+ *        matrix and phenotype at ingest                 -> vampomi_set_adjust / vampomi_read_adjust
  *
  * Testing aid: with VAMPOMI_COMM=loopback in the environment, the contexts
  * of a multi-rank job are driven by threads of ONE process (any device, the
@@ -268,6 +270,65 @@ vampomi_status vampomi_get_meth_na(const vampomi_ctx* ctx, int* policy, double* 
  * VAMPOMI_NA_PASS.  VAMPOMI_ERR_STATE before a shard is loaded. */
 vampomi_status vampomi_get_missing_stats(const vampomi_ctx* ctx, int64_t* missing, int64_t* markers_with_missing,
                                          int64_t* markers_masked, int64_t* per_marker);
+/* ---- covariate adjustment of the LINEAR model ----
+ * By Frisch-Waugh, y = Z g + X b + e with a flat prior on g is the model
+ * P y = P X b + P e, P = I - Q Q^T, Q an orthonormal basis of span{1, Z}.  An
+ * adjusted context stores P X and P y at ingest; nothing after the load knows
+ * of it (operators, CG, denoiser, EM, association tests, test mode).
+ *
+ * vampomi_adjust_basis needs no device.  Z: C columns (0 <= C <= VAMPOMI_MAX_C)
+ * of n raw values, column stride ld_in >= n; a value that is not finite is
+ * VAMPOMI_ERR_ARG.  Q receives n x R doubles, column-major, R <= C + 1 (have
+ * room for C + 1 columns): modified Gram-Schmidt over the intercept (always
+ * kept, always first: Q's first column is 1/sqrt(n)) and then Z's columns in
+ * order, each vector orthogonalised twice against the accepted ones, every sum
+ * in long double, the normalised vector rounded to double.  dropped (C flags;
+ * may be NULL when C == 0): 1 for a column whose norm is 0 or, after the
+ * orthogonalisation, at most 1e-8 of what it was (constant or dependent).
+ *
+ * vampomi_set_adjust: the table for the context's N rows (C == 0: the
+ * intercept only).  Legal only before the shard is allocated and before a
+ * phenotype is set, and after vampomi_set_row_subset if there is one (which
+ * returns VAMPOMI_ERR_STATE on an adjusted context): VAMPOMI_ERR_STATE
+ * otherwise.  Residuals leave [0, 1]: VAMPOMI_ERR_ARG on a VAMPOMI_STORE_U16
+ * context, and from vampomi_set_storage(VAMPOMI_STORE_U16) on an adjusted one
+ * (uint16 INPUT into F64 / F32 storage is fine: widened, then adjusted).
+ * vampomi_read_adjust: the file parsed as vampomi_parse_covariates(..,
+ * standardize = 0) with N_file rows of which the subset's are taken.  Rank-local
+ * and without a collective: every rank sets the same table and computes the
+ * same bits.  From then on
+ *   - every vampomi_load_meth_* adjusts each marker after the row gather and the
+ *     NaN fill, in fp64: x the column (kept rows, missing entries filled as
+ *     VAMPOMI_NA_MEAN defines), c = Q^T x, r = x - Q c, every sum in a fixed
+ *     order that depends on N and R alone.  F64 stores r, F32
+ *     (float)r: one rounding.  A marker with |r|^2 <= 1e-20 |x|^2 (constant,
+ *     inside the covariates' span, all zero, masked) is ABSORBED: stored as
+ *     zeros, a constant column (mave 0, msig 1, exactly null), and counted;
+ *   - vampomi_read_phen and vampomi_set_phen replace y by y - Q (Q^T y) (host,
+ *     long double sums) before their standardize step; vampomi_get_phen returns
+ *     the adjusted, then scaled, vector;
+ *   - vampomi_generate_meth, and vampomi_vamp_begin / vampomi_infere with
+ *     "bin_class" (the probit model has its own covariates), return
+ *     VAMPOMI_ERR_STATE.
+ * The context holds what vampomi_read_markers and vampomi_get_phen return and
+ * computes, bit for bit, what a plain context of the same storage computes
+ * after vampomi_load_meth_host of that matrix and vampomi_set_phen(.., 0) of
+ * that vector; the stored bits depend on neither the chunk size, file or array
+ * input, nor the rank count, and an F32 context holds (float) of what an F64
+ * one holds.  The association test's p-values keep N - 2 degrees of freedom, as
+ * after an offline adjustment.  Without an adjustment every load is what it is
+ * without these calls, launch for launch. */
+vampomi_status vampomi_adjust_basis(const double* Z, int64_t n, int C, int64_t ld_in, double* Q, int* R,
+                                    int* dropped);
+vampomi_status vampomi_set_adjust(vampomi_ctx* ctx, const double* Z, int C, int64_t ld_in);
+vampomi_status vampomi_read_adjust(vampomi_ctx* ctx, const char* path, int C);
+/* *R = the basis vectors (0: no adjustment), dropped: the table's C flags, Q:
+ * N x R doubles.  Every pointer may be NULL. */
+vampomi_status vampomi_get_adjust(const vampomi_ctx* ctx, int* R, int* dropped, double* Q);
+/* The last load: the absorbed markers of this rank's shard and per_marker (M
+ * flags, host).  Either pointer may be NULL.  Zeros without an adjustment.
+ * VAMPOMI_ERR_STATE before a shard is loaded. */
+vampomi_status vampomi_get_adjust_stats(const vampomi_ctx* ctx, int64_t* absorbed, uint8_t* per_marker);
 /* synthetic shard generated on the device (bit-identical to the oracle's; an
  * F32 context stores the generator's value rounded: VAMPOMI_GEN_GAUSS values
  * are exactly floats, VAMPOMI_GEN_METH values are not; a U16 context stores
@@ -293,7 +354,7 @@ vampomi_status vampomi_simulate_phen_binary(vampomi_ctx* ctx, uint64_t seed, dou
  * y is.  A context that holds one (C > 0) fits the covariate effects at the
  * start of every bin_class run and offsets the z-side denoiser with them
  * (below); the LINEAR model ignores the table, as the reference's main_meth.exe
- * does.  Two properties of the reference's fit that are kept: a constant column
+ * does (its covariates are regressed out at ingest: vampomi_set_adjust).  Two properties of the reference's fit that are kept: a constant column
  * standardises to zeros and makes the Newton matrix singular, so the fit
  * returns ALL effects zero; and no intercept is fitted unless the table
  * carries a (non-constant) column for one.

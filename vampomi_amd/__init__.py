@@ -24,7 +24,7 @@ from ._lib import (CLI_PATH, GEN_GAUSS, GEN_METH, LIB_PATH, MAX_L, MEM_DEVICE, M
                    STORE_F32, STORE_F64, STORE_U16, UNIQUE_ID_BYTES, Params, Result, ShardDesc, Stats, VampomiError,
                    check, load)
 
-__all__ = ["Data", "Vamp", "VampOptions", "divide_work", "comm_unique_id", "phen_rows", "VampomiError", "LIB_PATH", "CLI_PATH",
+__all__ = ["Data", "Vamp", "VampOptions", "divide_work", "comm_unique_id", "phen_rows", "adjust_basis", "VampomiError", "LIB_PATH", "CLI_PATH",
            "GEN_GAUSS", "GEN_METH", "STORE_F64", "STORE_F32", "STORE_U16", "load"]
 
 _STORAGE = {"f64": STORE_F64, "f32": STORE_F32, "u16": STORE_U16}
@@ -64,6 +64,24 @@ def phen_rows(path: str, keep_file: Optional[str] = None, drop_na: bool = False)
     check(lib.vampomi_phen_rows(path.encode(), keep, 1 if drop_na else 0, _dp(rows), n.value, C.byref(nf),
                                 C.byref(n)))
     return rows[: n.value], nf.value
+
+
+def adjust_basis(Z: np.ndarray):
+    """(Q, dropped): the orthonormal basis of span{1, Z} that a covariate
+    adjustment projects out (vampomi_adjust_basis; no device needed).  ``Z``:
+    (n, C) raw covariates, C >= 0.  ``Q``: (n, R), its first column the
+    intercept's 1/sqrt(n); ``dropped``: C booleans, the constant or dependent
+    columns of ``Z``."""
+    Z = np.asarray(Z, dtype=np.float64)
+    if Z.ndim != 2:
+        raise ValueError("Z must be (n, C)")
+    n, nc = Z.shape
+    Zc = np.ascontiguousarray(Z.T)  # covariate-major
+    Q = np.zeros((nc + 1, max(n, 1)))
+    dropped = np.zeros(max(nc, 1), dtype=np.int32)
+    R = C.c_int()
+    check(load().vampomi_adjust_basis(_dp(Zc), n, nc, n, _dp(Q), C.byref(R), _dp(dropped)))
+    return np.ascontiguousarray(Q[: R.value].T), dropped[:nc].astype(bool)
 
 
 class Data:
@@ -107,11 +125,27 @@ class Data:
     exactly null.  Everything after the load treats the filled matrix
     (:meth:`get_meth_data`) as the data.  :meth:`missing_stats` and
     :meth:`missing_counts` tell what the last load found.
+
+    ``adjust``: covariates to regress out of the LINEAR model's data at ingest,
+    an intercept always with them.  Either a ``(d.N, C)`` array of raw values
+    (the kept rows; ``C`` may be 0: the intercept only), or the path of a
+    covariate file together with ``adjust_C``, its number of columns (the file
+    has ``N_file`` rows, of which a row subset's are taken).  Every load then
+    stores each marker's residual on span{1, Z} (after the row gather and the
+    ``meth_na`` fill, in fp64, rounded once into ``"f32"``; ``"u16"`` cannot
+    hold residuals: status 1), a marker inside that span is stored as zeros
+    (absorbed), and :meth:`read_phen` / :meth:`set_phen` project the phenotype
+    the same way before they scale it.  :meth:`adjust_info` and
+    :meth:`adjust_stats` tell the rest.  :meth:`generate` and the
+    ``"bin_class"`` model raise status 6 on such a context.
     """
 
     def __init__(self, N: int, Mt: int, rank: int = 0, nranks: int = 1, comm_id: Optional[bytes] = None,
                  device: int = -1, alpha_scale: float = 1.0, storage: Optional[str] = None,
-                 rows: Optional[Sequence[int]] = None, meth_na: Optional[str] = None, max_missing_frac: float = 1.0):
+                 rows: Optional[Sequence[int]] = None, meth_na: Optional[str] = None, max_missing_frac: float = 1.0,
+                 adjust=None, adjust_C: Optional[int] = None):
+        if isinstance(adjust, str) != (adjust_C is not None):
+            raise ValueError("adjust_C goes with adjust=<path of a covariate file>, and only with it")
         if storage is not None and storage not in _STORAGE:
             raise ValueError(f'storage must be "f64", "f32" or "u16", not {storage!r}')
         if meth_na is not None and meth_na not in _METH_NA:
@@ -144,6 +178,36 @@ class Data:
             check(self._lib.vampomi_set_row_subset(self.ctx, self.N_file, _dp(self.rows), len(self.rows)))
         if meth_na is not None:
             check(self._lib.vampomi_set_meth_na(self.ctx, _METH_NA[meth_na], max_missing_frac))
+        if isinstance(adjust, str):
+            check(self._lib.vampomi_read_adjust(self.ctx, adjust.encode(), adjust_C))
+        elif adjust is not None:
+            Z = np.asarray(adjust, dtype=np.float64)
+            if Z.ndim != 2 or Z.shape[0] != self.N:
+                raise ValueError(f"adjust must be ({self.N}, C), got {Z.shape}")
+            Zc = np.ascontiguousarray(Z.T)  # covariate-major
+            check(self._lib.vampomi_set_adjust(self.ctx, _dp(Zc) if Z.shape[1] else None, Z.shape[1], self.N))
+
+    def adjust_info(self) -> dict:
+        """The adjustment: ``R`` basis vectors (0: none), ``dropped`` (one
+        boolean per covariate column: constant or dependent) and ``Q``, (N, R),
+        the orthonormal basis, the intercept's column first."""
+        R = C.c_int()
+        check(self._lib.vampomi_get_adjust(self.ctx, C.byref(R), None, None))
+        dropped = np.zeros(65, dtype=np.int32)
+        dropped[:] = -1
+        Q = np.zeros((max(R.value, 1), self.N))
+        check(self._lib.vampomi_get_adjust(self.ctx, None, _dp(dropped), _dp(Q)))
+        return {"R": R.value, "dropped": dropped[dropped >= 0].astype(bool),
+                "Q": np.ascontiguousarray(Q[: R.value].T)}
+
+    def adjust_stats(self) -> dict:
+        """What the last load's adjustment did to this shard: ``absorbed``, the
+        markers stored as zeros because nothing of them was left outside the
+        covariates' span, and ``flags``, one boolean per local marker."""
+        n = C.c_int64()
+        flags = np.zeros(max(self.M, 1), dtype=np.uint8)
+        check(self._lib.vampomi_get_adjust_stats(self.ctx, C.byref(n), _dp(flags)))
+        return {"absorbed": n.value, "flags": flags[: self.M].astype(bool)}
 
     @property
     def meth_na(self) -> str:

@@ -125,6 +125,11 @@ SIGNATURES = {
     "vampomi_set_meth_na": (C.c_int, [_P, C.c_int, C.c_double]),
     "vampomi_get_meth_na": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "vampomi_get_missing_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
+    "vampomi_adjust_basis": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int64, _P, C.POINTER(C.c_int), _P]),
+    "vampomi_set_adjust": (C.c_int, [_P, _P, C.c_int, C.c_int64]),
+    "vampomi_read_adjust": (C.c_int, [_P, C.c_char_p, C.c_int]),
+    "vampomi_get_adjust": (C.c_int, [_P, C.POINTER(C.c_int), _P, _P]),
+    "vampomi_get_adjust_stats": (C.c_int, [_P, C.POINTER(C.c_int64), _P]),
     "vampomi_generate_meth": (C.c_int, [_P, C.c_uint64, C.c_int]),
     "vampomi_read_phen": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "vampomi_set_phen": (C.c_int, [_P, _P, C.c_int]),

@@ -117,6 +117,23 @@ struct vampomi_ctx {
     int64_t N_file = 0;
     std::vector<int64_t> rows_host;
     int32_t* rows_dev = nullptr;
+    // covariate adjustment (vampomi_set_adjust; adj_R == 0: none; fixed once X is
+    // allocated): adj_Q, N x adj_R orthonormal doubles, column-major, the
+    // intercept's first; adj_dropped, one flag per column of the table.  During
+    // a load only (adjust_begin .. adjust_end, engine.cpp): the device copy of
+    // Q, put_cols' fp64 work block, and the absorbed flags and counter that
+    // vk::adjust_cols fills; adj_flags / adj_absorbed are their host copy
+    // (vampomi_get_adjust_stats)
+    int adj_R = 0, adj_C = 0;
+    std::vector<double> adj_Q;
+    std::vector<int> adj_dropped;
+    double* adj_Qdev = nullptr;
+    double* adj_work = nullptr;
+    size_t adj_work_cap = 0;  // bytes
+    uint8_t* adj_flags_dev = nullptr;
+    unsigned long long* adj_cnt_dev = nullptr;
+    std::vector<uint8_t> adj_flags;  // empty: all zeros
+    int64_t adj_absorbed = 0;
     double* mave = nullptr;
     double* msig = nullptr;
     double* y = nullptr;     // ld, zero pad

@@ -1322,6 +1322,8 @@ extern "C" vampomi_status vampomi_set_storage(vampomi_ctx* c, int storage) {
     if (storage != VAMPOMI_STORE_F64 && storage != VAMPOMI_STORE_F32 && storage != VAMPOMI_STORE_U16)
         return fail(VAMPOMI_ERR_ARG, "storage must be VAMPOMI_STORE_F64, VAMPOMI_STORE_F32 or VAMPOMI_STORE_U16");
     if (c->X) return fail(VAMPOMI_ERR_STATE, "the storage is fixed once the methylation shard is allocated");
+    if (storage == VAMPOMI_STORE_U16 && c->adj_R)
+        return fail(VAMPOMI_ERR_ARG, "covariate-adjusted values leave [0, 1]: VAMPOMI_STORE_U16 cannot hold them");
     c->storage = storage;
     return VAMPOMI_OK;
 }
@@ -1356,6 +1358,7 @@ extern "C" vampomi_status vampomi_set_row_subset(vampomi_ctx* c, int64_t N_file,
     if (c->X) return fail(VAMPOMI_ERR_STATE, "the row subset is fixed once the methylation shard is allocated");
     if (c->have_y || c->cov_C > 0)
         return fail(VAMPOMI_ERR_STATE, "set the row subset before the phenotype and the covariates");
+    if (c->adj_R) return fail(VAMPOMI_ERR_STATE, "set the row subset before the covariate adjustment");
     if (N_file >= ((int64_t)1 << 31)) return fail(VAMPOMI_ERR_ARG, "row subset: N_file must be below 2^31");
     if (n != c->N)
         return fail(VAMPOMI_ERR_ARG, "row subset: n (" + std::to_string(n) + ") != the context's N (" +
@@ -1388,6 +1391,176 @@ extern "C" vampomi_status vampomi_get_row_subset(const vampomi_ctx* c, int64_t* 
 
 // the rows of a column of the input: the file's with a row subset, else N
 static int64_t rows_in(const vampomi_ctx* c) { return c->N_file ? c->N_file : c->N; }
+
+// ---------------------------------------------------------------------------
+// covariate adjustment of the linear model: X and y are
+// replaced at ingest by their residuals on span{1, Z}
+// ---------------------------------------------------------------------------
+// Modified Gram-Schmidt over the intercept, then Z's columns in order: each
+// vector is orthogonalised twice against the accepted ones, every sum in long
+// double, and rounded to double once it is normalised.  A column whose norm is
+// 0, or at most 1e-8 of it after the orthogonalisation, is dropped.
+extern "C" vampomi_status vampomi_adjust_basis(const double* Z, int64_t n, int C, int64_t ld_in, double* Q, int* R,
+                                               int* dropped) {
+    if (C < 0 || C > VAMPOMI_MAX_C)
+        return fail(VAMPOMI_ERR_ARG, "number of covariates out of range (0.." + std::to_string(VAMPOMI_MAX_C) + ")");
+    if (n < 1 || !Q || !R || (C > 0 && (!Z || !dropped || ld_in < n))) return fail(VAMPOMI_ERR_ARG, "bad covariate table");
+    for (int i = 0; i < C; ++i)
+        for (int64_t j = 0; j < n; ++j)
+            if (!std::isfinite(Z[(int64_t)i * ld_in + j]))
+                return fail(VAMPOMI_ERR_ARG, "covariate " + std::to_string(i) + ", row " + std::to_string(j) +
+                                                 " is not finite");
+    std::vector<long double> v((size_t)n);
+    const auto norm = [&] {
+        long double s = 0.0L;
+        for (int64_t j = 0; j < n; ++j) s += v[(size_t)j] * v[(size_t)j];
+        return std::sqrt(s);
+    };
+    int r = 0;
+    for (int i = -1; i < C; ++i) {  // -1: the intercept
+        for (int64_t j = 0; j < n; ++j) v[(size_t)j] = i < 0 ? 1.0L : (long double)Z[(int64_t)i * ld_in + j];
+        const long double before = norm();
+        bool keep = before > 0.0L;
+        if (keep) {
+            for (int pass = 0; pass < 2; ++pass)
+                for (int k = 0; k < r; ++k) {
+                    const double* q = Q + (size_t)k * (size_t)n;
+                    long double d = 0.0L;
+                    for (int64_t j = 0; j < n; ++j) d += (long double)q[j] * v[(size_t)j];
+                    for (int64_t j = 0; j < n; ++j) v[(size_t)j] -= d * (long double)q[j];
+                }
+            const long double after = norm();
+            keep = after > 1e-8L * before;
+            if (keep) {
+                double* q = Q + (size_t)r * (size_t)n;
+                for (int64_t j = 0; j < n; ++j) q[j] = (double)(v[(size_t)j] / after);
+                ++r;
+            }
+        }
+        if (i >= 0) dropped[i] = keep ? 0 : 1;
+    }
+    *R = r;
+    return VAMPOMI_OK;
+}
+
+extern "C" vampomi_status vampomi_set_adjust(vampomi_ctx* c, const double* Z, int C, int64_t ld_in) {
+    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
+    if (C < 0 || C > VAMPOMI_MAX_C)
+        return fail(VAMPOMI_ERR_ARG, "number of covariates out of range (0.." + std::to_string(VAMPOMI_MAX_C) + ")");
+    if (C > 0 && (!Z || ld_in < c->N)) return fail(VAMPOMI_ERR_ARG, "bad covariate table");
+    if (c->u16())
+        return fail(VAMPOMI_ERR_ARG, "covariate-adjusted values leave [0, 1]: VAMPOMI_STORE_U16 cannot hold them");
+    if (c->X) return fail(VAMPOMI_ERR_STATE, "the adjustment is fixed once the methylation shard is allocated");
+    if (c->have_y) return fail(VAMPOMI_ERR_STATE, "set the adjustment before the phenotype");
+    std::vector<double> Q((size_t)(C + 1) * (size_t)c->N);
+    std::vector<int> dropped((size_t)C, 0);
+    int R = 0;
+    STCHK(vampomi_adjust_basis(Z, c->N, C, ld_in, Q.data(), &R, dropped.data()));
+    Q.resize((size_t)R * (size_t)c->N);
+    c->adj_Q.swap(Q);
+    c->adj_dropped.swap(dropped);
+    c->adj_R = R;
+    c->adj_C = C;
+    return VAMPOMI_OK;
+}
+
+extern "C" vampomi_status vampomi_read_adjust(vampomi_ctx* c, const char* path, int C) {
+    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
+    if (C < 0 || C > VAMPOMI_MAX_C)
+        return fail(VAMPOMI_ERR_ARG, "number of covariates out of range (0.." + std::to_string(VAMPOMI_MAX_C) + ")");
+    if (C == 0) return vampomi_set_adjust(c, nullptr, 0, c->N);
+    const int64_t Nin = c->N_file ? c->N_file : c->N;
+    std::vector<double> raw((size_t)C * (size_t)Nin);
+    STCHK(vampomi_parse_covariates(path, Nin, C, 0, raw.data()));
+    if (!c->N_file) return vampomi_set_adjust(c, raw.data(), C, c->N);
+    std::vector<double> Z((size_t)C * (size_t)c->N);
+    for (int j = 0; j < C; ++j)
+        for (int64_t i = 0; i < c->N; ++i)
+            Z[(size_t)j * c->N + i] = raw[(size_t)j * c->N_file + c->rows_host[(size_t)i]];
+    return vampomi_set_adjust(c, Z.data(), C, c->N);
+}
+
+extern "C" vampomi_status vampomi_get_adjust(const vampomi_ctx* c, int* R, int* dropped, double* Q) {
+    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
+    if (R) *R = c->adj_R;
+    if (dropped) std::copy(c->adj_dropped.begin(), c->adj_dropped.end(), dropped);
+    if (Q && c->adj_R) std::memcpy(Q, c->adj_Q.data(), c->adj_Q.size() * sizeof(double));
+    return VAMPOMI_OK;
+}
+
+extern "C" vampomi_status vampomi_get_adjust_stats(const vampomi_ctx* c, int64_t* absorbed, uint8_t* per_marker) {
+    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
+    if (!c->have_X) return fail(VAMPOMI_ERR_STATE, "no methylation data loaded");
+    if (absorbed) *absorbed = c->adj_absorbed;
+    if (per_marker && c->adj_flags.empty()) std::fill(per_marker, per_marker + c->M, (uint8_t)0);
+    if (per_marker && !c->adj_flags.empty()) std::copy(c->adj_flags.begin(), c->adj_flags.end(), per_marker);
+    return VAMPOMI_OK;
+}
+
+// y <- y - Q (Q^T y) on an adjusted context, long double sums, rounded once
+static void adjust_phen(const vampomi_ctx* c, std::vector<double>& y) {
+    if (!c->adj_R) return;
+    const size_t n = (size_t)c->N;
+    std::vector<long double> r(y.begin(), y.end());
+    for (int k = 0; k < c->adj_R; ++k) {
+        const double* q = c->adj_Q.data() + (size_t)k * n;
+        long double d = 0.0L;
+        for (size_t j = 0; j < n; ++j) d += (long double)q[j] * (long double)y[j];
+        for (size_t j = 0; j < n; ++j) r[j] -= d * (long double)q[j];
+    }
+    for (size_t j = 0; j < n; ++j) y[j] = (double)r[j];
+}
+
+// The device side of an adjusted load: Q, the absorbed flags and the counter
+// from adjust_begin (after ensure_X) and put_cols' work block live until
+// adjust_free, which every exit path of a load reaches (AdjustLoad).  Without
+// an adjustment nothing is allocated and nothing is launched.
+static void adjust_free(vampomi_ctx* c) {
+    if (!c->adj_Qdev && !c->adj_work && !c->adj_flags_dev && !c->adj_cnt_dev) return;
+    (void)hipStreamSynchronize(c->st);
+    if (c->adj_Qdev) (void)hipFree(c->adj_Qdev);
+    if (c->adj_work) (void)hipFree(c->adj_work);
+    if (c->adj_flags_dev) (void)hipFree(c->adj_flags_dev);
+    if (c->adj_cnt_dev) (void)hipFree(c->adj_cnt_dev);
+    c->adj_Qdev = c->adj_work = nullptr;
+    c->adj_flags_dev = nullptr;
+    c->adj_cnt_dev = nullptr;
+    c->adj_work_cap = 0;
+}
+
+struct AdjustLoad {
+    vampomi_ctx* c;
+    ~AdjustLoad() { adjust_free(c); }
+};
+
+static vampomi_status adjust_begin(vampomi_ctx* c) {
+    c->adj_absorbed = 0;
+    c->adj_flags.clear();
+    if (!c->adj_R) return VAMPOMI_OK;
+    const size_t qb = c->adj_Q.size() * sizeof(double), fb = (size_t)std::max<int64_t>(c->M, 1);
+    if (hipMalloc((void**)&c->adj_Qdev, qb) != hipSuccess || hipMalloc((void**)&c->adj_flags_dev, fb) != hipSuccess ||
+        hipMalloc((void**)&c->adj_cnt_dev, sizeof(unsigned long long)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VAMPOMI_ERR_OOM, "covariate basis on the device");
+    }
+    HIPCHK(hipMemcpyAsync(c->adj_Qdev, c->adj_Q.data(), qb, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemsetAsync(c->adj_flags_dev, 0, fb, c->st));
+    HIPCHK(hipMemsetAsync(c->adj_cnt_dev, 0, sizeof(unsigned long long), c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    return VAMPOMI_OK;
+}
+
+static vampomi_status adjust_end(vampomi_ctx* c) {
+    if (!c->adj_R) return VAMPOMI_OK;
+    unsigned long long n = 0;
+    c->adj_flags.assign((size_t)c->M, 0);
+    HIPCHK(hipMemcpyAsync(&n, c->adj_cnt_dev, sizeof n, hipMemcpyDeviceToHost, c->st));
+    if (c->M > 0)
+        HIPCHK(hipMemcpyAsync(c->adj_flags.data(), c->adj_flags_dev, (size_t)c->M, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    c->adj_absorbed = (int64_t)n;
+    return VAMPOMI_OK;
+}
 
 static vampomi_status finish_X(vampomi_ctx* c) {
     const size_t es = (size_t)c->esize();
@@ -1536,7 +1709,36 @@ static vampomi_status put_cols(vampomi_ctx* c, int64_t i0, int64_t nc, const voi
     if (nc <= 0) return VAMPOMI_OK;
     const size_t es = (size_t)c->esize();
     char* dst = (char*)c->X + (size_t)i0 * (size_t)c->ld * es;
-    if ((size_t)in_es == es && !c->N_file && !na_active(c, in_es)) {
+    // An adjusted context: the same conversions, pointed at an fp64 work block
+    // of packed columns (the row gather and the NaN fill come first), which
+    // vk::adjust_cols then empties into the shard: one rounding into F32.
+    double* work = nullptr;
+    if (c->adj_R) {
+        const size_t wb = (size_t)nc * (size_t)c->N * 8;
+        if (c->adj_work_cap < wb) {
+            HIPCHK(hipStreamSynchronize(c->st));
+            if (c->adj_work) (void)hipFree(c->adj_work);
+            c->adj_work = nullptr;
+            c->adj_work_cap = 0;
+            if (hipMalloc((void**)&c->adj_work, wb) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(VAMPOMI_ERR_OOM, "device work block of the covariate adjustment");
+            }
+            c->adj_work_cap = wb;
+        }
+        work = c->adj_work;
+    }
+    const auto adjust = [&]() -> vampomi_status {
+        HIPCHK(vk::adjust_cols(work, c->N, nc, c->adj_Qdev, c->adj_R, dst, c->ek(), c->ld, c->adj_flags_dev + i0,
+                               c->adj_cnt_dev, c->st));
+        return VAMPOMI_OK;
+    };
+    if (work && in_es == 8 && !c->N_file && !na_active(c, in_es)) {  // doubles as they are: no staging hop
+        HIPCHK(hipMemcpy2DAsync(work, (size_t)c->N * 8, src, (size_t)ld_in * 8, (size_t)c->N * 8, (size_t)nc,
+                                hipMemcpyHostToDevice, c->st));
+        return adjust();
+    }
+    if (!work && (size_t)in_es == es && !c->N_file && !na_active(c, in_es)) {
         HIPCHK(hipMemcpy2DAsync(dst, (size_t)c->ld * es, src, (size_t)ld_in * es, (size_t)c->N * es, (size_t)nc,
                                 hipMemcpyHostToDevice, c->st));
         return VAMPOMI_OK;
@@ -1556,6 +1758,20 @@ static vampomi_status put_cols(vampomi_ctx* c, int64_t i0, int64_t nc, const voi
     }
     HIPCHK(hipMemcpy2DAsync(*stage, (size_t)Nin * in_es, src, (size_t)ld_in * in_es, (size_t)Nin * in_es,
                             (size_t)nc, hipMemcpyHostToDevice, c->st));
+    if (work) {
+        const int sek = in_es == 2 ? vk::kXU16 : in_es == 4 ? vk::kXF32 : vk::kXF64;
+        if (na_active(c, in_es))
+            HIPCHK(vk::na_ingest_cols(*stage, sek, Nin, c->rows_dev, c->N, nc, work, vk::kXF64, c->N, Nin, c->S + i0,
+                                      c->na_policy, c->na_max_frac, c->na_cnt + i0, c->na_rec, nullptr, c->st));
+        else if (c->N_file)
+            HIPCHK(vk::gather_cols(*stage, sek, Nin, c->rows_dev, c->N, nc, work, vk::kXF64, c->N, Nin, c->S + i0,
+                                   nullptr, c->st));
+        else if (in_es == 2)
+            HIPCHK(vk::dequant_cols((const uint16_t*)*stage, c->N, c->N, nc, work, c->N, c->st));
+        else
+            HIPCHK(vk::widen_cols((const float*)*stage, c->N, c->N, nc, work, c->N, c->st));
+        return adjust();
+    }
     if (na_active(c, in_es))
         HIPCHK(vk::na_ingest_cols(*stage, in_es == 4 ? vk::kXF32 : vk::kXF64, Nin, c->rows_dev, c->N, nc, dst, c->ek(),
                                   c->ld, Nin, c->S + i0, c->na_policy, c->na_max_frac, c->na_cnt + i0, c->na_rec,
@@ -1590,10 +1806,12 @@ static vampomi_status load_host(vampomi_ctx* c, const void* X, int64_t ld_in, in
     STCHK(quant_begin(c));
     const bool look = na_active(c, in_es);
     STCHK(na_begin(c, look));
+    AdjustLoad adj_{c};
+    STCHK(adjust_begin(c));
     void* stage = nullptr;
     size_t cap = 0;
     vampomi_status st = VAMPOMI_OK;
-    const int64_t chunk = (int64_t)in_es == c->esize() && !c->N_file && !look
+    const int64_t chunk = (int64_t)in_es == c->esize() && !c->N_file && !look && !c->adj_R
                               ? std::max<int64_t>(c->M, 1)
                               : std::max<int64_t>(1, io_chunk_bytes() / (rows_in(c) * in_es));
     for (int64_t i0 = 0; i0 < c->M && st == VAMPOMI_OK; i0 += chunk)
@@ -1606,6 +1824,7 @@ static vampomi_status load_host(vampomi_ctx* c, const void* X, int64_t ld_in, in
     if (st != VAMPOMI_OK) return st;
     STCHK(na_end(c, look));
     STCHK(quant_end(c));
+    STCHK(adjust_end(c));
     return finish_X(c);
 }
 
@@ -1676,6 +1895,11 @@ static vampomi_status load_file(vampomi_ctx* c, const char* path, int in_es) {
         ::close(fd);
         return s0;
     }
+    AdjustLoad adj_{c};
+    if (const vampomi_status s0 = adjust_begin(c)) {
+        ::close(fd);
+        return s0;
+    }
     const size_t colb = (size_t)rows_in(c) * (size_t)in_es;
     const size_t chunk_cols = std::max<size_t>(1, (size_t)io_chunk_bytes() / colb);
     const char* env = std::getenv("VAMPOMI_IO_THREADS");
@@ -1726,6 +1950,7 @@ static vampomi_status load_file(vampomi_ctx* c, const char* path, int in_es) {
     if (st != VAMPOMI_OK) return st;
     STCHK(na_end(c, look));
     STCHK(quant_end(c));
+    STCHK(adjust_end(c));
     return finish_X(c);
 }
 
@@ -1742,6 +1967,8 @@ extern "C" vampomi_status vampomi_load_meth_file_u16(vampomi_ctx* c, const char*
 extern "C" vampomi_status vampomi_generate_meth(vampomi_ctx* c, uint64_t seed, int kind) {
     if (!c || (kind != VAMPOMI_GEN_GAUSS && kind != VAMPOMI_GEN_METH)) return fail(VAMPOMI_ERR_ARG, "bad argument");
     if (c->N_file) return fail(VAMPOMI_ERR_STATE, "a context with a row subset loads its shard from a file or the host");
+    if (c->adj_R)
+        return fail(VAMPOMI_ERR_STATE, "a covariate-adjusted context loads its shard from a file or the host");
     if (c->u16() && kind == VAMPOMI_GEN_GAUSS)
         return fail(VAMPOMI_ERR_RANGE, "VAMPOMI_GEN_GAUSS values are not in [0, 1]: they cannot be stored as 16-bit "
                                        "fixed point (VAMPOMI_STORE_U16)");
@@ -1749,6 +1976,7 @@ extern "C" vampomi_status vampomi_generate_meth(vampomi_ctx* c, uint64_t seed, i
     STCHK(ensure_X(c));
     STCHK(quant_begin(c));
     STCHK(na_begin(c, false));
+    STCHK(adjust_begin(c));  // (no adjustment here: the last load's record is forgotten)
     if (!c->u16()) {
         HIPCHK(vk::gen_markers(seed, kind, c->N, c->ld, c->S, c->M, c->X, c->ek(), c->st));
         return finish_X(c);
@@ -1808,6 +2036,7 @@ extern "C" vampomi_status vampomi_read_phen(vampomi_ctx* c, const char* path, in
             return fail(VAMPOMI_ERR_ARG,
                         "phenotype rows (" + std::to_string(n) + ") != N (" + std::to_string(c->N) + ")");
     }
+    adjust_phen(c, y);
     if (standardize) vio::standardize_phen(y);
     c->y_host = y;
     return upload_phen(c);
@@ -1817,6 +2046,7 @@ extern "C" vampomi_status vampomi_set_phen(vampomi_ctx* c, const double* y, int 
     if (!c || !y) return fail(VAMPOMI_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(c->device));
     c->y_host.assign(y, y + c->N);
+    adjust_phen(c, c->y_host);
     if (standardize) vio::standardize_phen(c->y_host);
     return upload_phen(c);
 }

@@ -361,6 +361,18 @@ enum { kNaFatal = 1, kNaMean = 2 };  // (VAMPOMI_NA_FATAL / VAMPOMI_NA_MEAN)
 hipError_t na_ingest_cols(const void* src, int src_ek, int64_t lds, const int32_t* rows, int64_t n, int64_t ncols,
                           void* dst, int dst_ek, int64_t ldd, int64_t nfile, int64_t col0, int mode, double max_frac,
                           int64_t* cnt, NaRec* nrec, QuantRec* qrec, hipStream_t st);
+// ---- covariate adjustment: the residual of each column on an orthonormal basis ---
+// src: an fp64 work block of ncols packed columns of n rows (what the ingest
+// conversions above leave with dst_ek = kXF64, ldd = n); Q: n x R doubles on
+// the device, column-major and packed, orthonormal (R <= kAdjMaxR).  Per column
+// c = Q^T x, r = x - Q c in fp64, stored as dst[col*ldd + j] = (XD)r_j (dst_ek
+// kXF64 or kXF32: one rounding); a column with ||r||^2 <= 1e-20 ||x||^2 is
+// stored as zeros, flags[col] = 1 (else 0) and *absorbed is incremented.  The
+// sums run in an order that depends on n and R alone (kernels.hip), so a
+// column's stored bits depend on neither the chunk nor the columns beside it.
+constexpr int kAdjMaxR = 65;  // VAMPOMI_MAX_C + 1: the intercept and every covariate
+hipError_t adjust_cols(const double* src, int64_t n, int64_t ncols, const double* Q, int R, void* dst, int dst_ek,
+                       int64_t ldd, uint8_t* flags, unsigned long long* absorbed, hipStream_t st);
 // beta_i = gauss(seed) for causal markers (uniform < lam), else 0; the count
 // of causal markers in ro.out[0]
 hipError_t gen_beta(uint64_t seed, double lam, int64_t S, int64_t M, double* beta, const RedOut& ro, hipStream_t st);

@@ -1994,6 +1994,134 @@ hipError_t na_ingest_cols(const void* src, int src_ek, int64_t lds, const int32_
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// covariate adjustment: r = x - Q (Q^T x), column by column
+// ---------------------------------------------------------------------------
+// A workgroup takes kAdjB columns at a time (grid-stride over the chunk's
+// column blocks), so every element of Q it reads serves kAdjB columns; thread t
+// owns rows t, t + 256, ... of all of them.
+//   1. c = Q^T x, kAdjKT basis vectors per sweep over the rows (kAdjB * kAdjKT
+//      running sums per thread; x is re-read out of L2 for every sweep).
+//   2. r = x - sum_k Q_k c_k, k ascending, one fma per term; r is stored as it
+//      is formed, ||x||^2 and ||r||^2 summed, and an absorbed column's rows are
+//      then overwritten with zeros by the threads that wrote them.
+// Every sum: the thread's rows ascending (fma), wave_sum's butterfly, the four
+// wave sums in wave order.  A column's sums are its own, so its bits depend on
+// n, R, Q and x alone: not on its block-mates (a short last block computes on
+// its first column again and stores nothing for it) nor on the chunk.
+static constexpr int kAdjB = 4, kAdjKT = 8;
+
+template <class XD>
+__global__ __launch_bounds__(kBlock) void adjust_kernel(const double* __restrict__ src, int64_t n, int64_t ncols,
+                                                        const double* __restrict__ Q, int R, XD* __restrict__ dst,
+                                                        int64_t ldd, uint8_t* __restrict__ flags,
+                                                        unsigned long long* __restrict__ absorbed) {
+    __shared__ double l_part[4][kAdjB * kAdjKT];
+    __shared__ double l_c[kAdjB][kAdjMaxR];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int64_t c0 = (int64_t)blockIdx.x * kAdjB; c0 < ncols; c0 += (int64_t)gridDim.x * kAdjB) {
+        const int nb = (int)(ncols - c0 < kAdjB ? ncols - c0 : kAdjB);
+        const double* __restrict__ col[kAdjB];
+#pragma unroll
+        for (int b = 0; b < kAdjB; ++b) col[b] = src + (c0 + (b < nb ? b : 0)) * n;
+        // 1. the coefficients
+        for (int k0 = 0; k0 < R; k0 += kAdjKT) {
+            double acc[kAdjB][kAdjKT];
+#pragma unroll
+            for (int b = 0; b < kAdjB; ++b)
+#pragma unroll
+                for (int kk = 0; kk < kAdjKT; ++kk) acc[b][kk] = 0.0;
+            for (int64_t j = threadIdx.x; j < n; j += kBlock) {
+                double x[kAdjB], q[kAdjKT];
+#pragma unroll
+                for (int b = 0; b < kAdjB; ++b) x[b] = col[b][j];
+#pragma unroll
+                for (int kk = 0; kk < kAdjKT; ++kk) q[kk] = k0 + kk < R ? Q[(int64_t)(k0 + kk) * n + j] : 0.0;
+#pragma unroll
+                for (int b = 0; b < kAdjB; ++b)
+#pragma unroll
+                    for (int kk = 0; kk < kAdjKT; ++kk) acc[b][kk] = fma(q[kk], x[b], acc[b][kk]);
+            }
+            __syncthreads();  // the previous sweep's partials have been read
+#pragma unroll
+            for (int b = 0; b < kAdjB; ++b)
+#pragma unroll
+                for (int kk = 0; kk < kAdjKT; ++kk) {
+                    const double s = wave_sum(acc[b][kk]);
+                    if (lane == 0) l_part[w][b * kAdjKT + kk] = s;
+                }
+            __syncthreads();
+            if (threadIdx.x < kAdjB * kAdjKT) {
+                const int i = threadIdx.x, k = k0 + i % kAdjKT;
+                if (k < R) l_c[i / kAdjKT][k] = ((l_part[0][i] + l_part[1][i]) + l_part[2][i]) + l_part[3][i];
+            }
+        }
+        __syncthreads();  // c is complete
+        // 2. the residual, stored as it is formed
+        double nx2[kAdjB], nr2[kAdjB];
+#pragma unroll
+        for (int b = 0; b < kAdjB; ++b) nx2[b] = nr2[b] = 0.0;
+        for (int64_t j = threadIdx.x; j < n; j += kBlock) {
+            double x[kAdjB], r[kAdjB];
+#pragma unroll
+            for (int b = 0; b < kAdjB; ++b) r[b] = x[b] = col[b][j];
+#pragma unroll 4
+            for (int k = 0; k < R; ++k) {
+                const double q = Q[(int64_t)k * n + j];
+#pragma unroll
+                for (int b = 0; b < kAdjB; ++b) r[b] = fma(-q, l_c[b][k], r[b]);
+            }
+#pragma unroll
+            for (int b = 0; b < kAdjB; ++b) {
+                nx2[b] = fma(x[b], x[b], nx2[b]);
+                nr2[b] = fma(r[b], r[b], nr2[b]);
+                if (b < nb) dst[(c0 + b) * ldd + j] = (XD)r[b];
+            }
+        }
+        __syncthreads();  // c and the last sweep's partials have been read
+#pragma unroll
+        for (int b = 0; b < kAdjB; ++b) {
+            const double sx = wave_sum(nx2[b]), sr = wave_sum(nr2[b]);
+            if (lane == 0) {
+                l_part[w][2 * b] = sx;
+                l_part[w][2 * b + 1] = sr;
+            }
+        }
+        __syncthreads();
+        // absorbed: ||r||^2 <= (1e-10)^2 ||x||^2 (an all-zero column too; a NaN never)
+#pragma unroll
+        for (int b = 0; b < kAdjB; ++b) {
+            if (b >= nb) break;
+            const double sx = ((l_part[0][2 * b] + l_part[1][2 * b]) + l_part[2][2 * b]) + l_part[3][2 * b];
+            const double sr =
+                ((l_part[0][2 * b + 1] + l_part[1][2 * b + 1]) + l_part[2][2 * b + 1]) + l_part[3][2 * b + 1];
+            const bool gone = sr <= 1e-20 * sx;  // (block-uniform)
+            if (threadIdx.x == 0) {
+                flags[c0 + b] = gone ? 1 : 0;
+                if (gone) atomicAdd(absorbed, 1ull);
+            }
+            if (gone)
+                for (int64_t j = threadIdx.x; j < n; j += kBlock) dst[(c0 + b) * ldd + j] = (XD)0;
+        }
+    }
+}
+
+hipError_t adjust_cols(const double* src, int64_t n, int64_t ncols, const double* Q, int R, void* dst, int dst_ek,
+                       int64_t ldd, uint8_t* flags, unsigned long long* absorbed, hipStream_t st) {
+    if (n <= 0 || ncols <= 0) return hipSuccess;
+    if (!src || !Q || !dst || !flags || !absorbed || R < 1 || R > kAdjMaxR || ldd < n ||
+        (dst_ek != kXF64 && dst_ek != kXF32))
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)std::min<int64_t>(cdiv(ncols, kAdjB), 65536));
+    if (dst_ek == kXF64)
+        hipLaunchKernelGGL(adjust_kernel<double>, grid, dim3(kBlock), 0, st, src, n, ncols, Q, R,
+                           static_cast<double*>(dst), ldd, flags, absorbed);
+    else
+        hipLaunchKernelGGL(adjust_kernel<float>, grid, dim3(kBlock), 0, st, src, n, ncols, Q, R,
+                           static_cast<float*>(dst), ldd, flags, absorbed);
+    return hipGetLastError();
+}
+
 __global__ __launch_bounds__(kBlock) void gen_beta_kernel(uint64_t seed, double lam, int64_t S, int64_t M,
                                                           double* beta, RedOut ro) {
     __shared__ double lds[4];

@@ -223,9 +223,26 @@ int main(int argc, char** argv) {
                 for (int64_t i = 0; i < n; ++i) kept[(size_t)j * n + i] = covs[(size_t)j * opt.N + rows[(size_t)i]];
             covs.swap(kept);
         }
-    } else if (opt.run_mode == "infere" && opt.C > 0 && rank == 0) {
+    } else if (opt.run_mode == "infere" && opt.C > 0 && rank == 0 && opt.cov_adjust != "residual") {
         std::cout << "INFO   : --C " << opt.C << ": covariates are used by --model bin_class only and are ignored"
                   << std::endl;
+    }
+    // --cov-adjust residual (the linear model; vopt::parse has checked the
+    // flags): the raw table of the files' rows, of which the kept ones are
+    // taken, on every rank before any device call, as above
+    const bool adjust = opt.cov_adjust == "residual";
+    std::vector<double> adj;
+    if (adjust) {
+        if (opt.C <= VAMPOMI_MAX_C) adj.assign((size_t)opt.C * (size_t)N_file, 0.0);
+        if (vampomi_parse_covariates((test_mode ? opt.cov_file_test : opt.cov_file).c_str(), N_file, (int)opt.C, 0,
+                                     adj.data()) != VAMPOMI_OK)
+            return die("covariate adjustment");
+        if (subset) {
+            std::vector<double> kept((size_t)opt.C * (size_t)n);
+            for (unsigned j = 0; j < opt.C; ++j)
+                for (int64_t i = 0; i < n; ++i) kept[(size_t)j * n + i] = adj[(size_t)j * N_file + rows[(size_t)i]];
+            adj.swap(kept);
+        }
     }
 
     unsigned char id[VAMPOMI_UNIQUE_ID_BYTES] = {0};
@@ -262,6 +279,19 @@ int main(int argc, char** argv) {
         vampomi_set_meth_na(ctx, opt.meth_na == "mean" ? VAMPOMI_NA_MEAN : VAMPOMI_NA_FATAL, opt.meth_na_max_frac) !=
             VAMPOMI_OK)
         return die("missing-value policy");
+    if (adjust) {  // (after the row subset, before the phenotype)
+        if (vampomi_set_adjust(ctx, adj.data(), (int)opt.C, n) != VAMPOMI_OK) return die("covariate adjustment");
+        int R = 0;
+        std::vector<int> dropped((size_t)opt.C, 0);
+        if (vampomi_get_adjust(ctx, &R, dropped.data(), nullptr) != VAMPOMI_OK) return die("covariate adjustment");
+        if (rank == 0) {
+            std::string names;
+            for (unsigned j = 0; j < opt.C; ++j)
+                if (dropped[j]) names += (names.empty() ? "" : ", ") + std::to_string(j);
+            std::cout << "INFO   : adjusting for " << R - 1 << " of " << opt.C << " covariates + intercept (dropped: "
+                      << (names.empty() ? "none" : names) << ")" << std::endl;
+        }
+    }
     // every rank has joined the communicator (its init is collective): the
     // rendezvous file has served and must not be read by a later job
     if (rank == 0 && !rdzv_path.empty()) vio::rdzv_remove(rdzv_path);
@@ -285,6 +315,13 @@ int main(int argc, char** argv) {
         if (missing)
             std::printf("INFO   : markers [%lld, %lld): %lld missing values in %lld markers, %lld masked\n",
                         (long long)S, (long long)(S + M), (long long)missing, (long long)with, (long long)masked);
+    }
+    if (adjust) {  // the markers of this rank's shard with nothing left outside the covariates' span
+        int64_t absorbed = 0;
+        if (vampomi_get_adjust_stats(ctx, &absorbed, nullptr) != VAMPOMI_OK) return die("covariate adjustment");
+        if (absorbed)
+            std::printf("INFO   : markers [%lld, %lld): %lld absorbed by the covariates\n", (long long)S,
+                        (long long)(S + M), (long long)absorbed);
     }
     // the ranks' shards load at their own pace (one rank's file may come off
     // slower storage): they meet here under a limit of their own, so the

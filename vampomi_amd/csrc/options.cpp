@@ -75,6 +75,7 @@ bool parse(int argc, char** argv, Options& o, std::string& echo) {
         {"--phen-na", {Kind::Str, &o.phen_na, nullptr}},
         {"--meth-na", {Kind::Str, &o.meth_na, nullptr}},
         {"--meth-na-max-frac", {Kind::Str, nullptr, nullptr}},
+        {"--cov-adjust", {Kind::Str, &o.cov_adjust, nullptr}},
     };
     std::stringstream ss;
     ss << "\nardyh command line options:\n";
@@ -108,6 +109,11 @@ bool parse(int argc, char** argv, Options& o, std::string& echo) {
                 if (name == "--meth-na" && std::strcmp(val, "pass") != 0 && std::strcmp(val, "fatal") != 0 &&
                     std::strcmp(val, "mean") != 0) {
                     std::cout << "FATAL  : option --meth-na has to be pass, fatal or mean! (" << val << " was passed)"
+                              << std::endl;
+                    return false;
+                }
+                if (name == "--cov-adjust" && std::strcmp(val, "none") != 0 && std::strcmp(val, "residual") != 0) {
+                    std::cout << "FATAL  : option --cov-adjust has to be none or residual! (" << val << " was passed)"
                               << std::endl;
                     return false;
                 }
@@ -179,6 +185,20 @@ bool parse(int argc, char** argv, Options& o, std::string& echo) {
         std::cout << "FATAL  : option --meth-na-max-frac needs --meth-na mean! (--meth-na is " << o.meth_na << ")"
                   << std::endl;
         return false;
+    }
+    if (o.cov_adjust == "residual") {
+        const bool test = o.run_mode == "test";
+        const char* why = o.model != "linear"                           ? "needs --model linear"
+                          : o.C < 1                                     ? "needs --C of at least 1"
+                          : (test ? o.cov_file_test : o.cov_file).empty() ? (test ? "needs --cov-file-test in --run-mode test"
+                                                                                 : "needs --cov-file")
+                          : o.meth_storage_set && o.meth_storage == "u16"
+                              ? "cannot be held by --meth-storage u16 (residuals leave [0, 1])"
+                              : nullptr;
+        if (why) {
+            std::cout << "FATAL  : option --cov-adjust residual " << why << "!" << std::endl;
+            return false;
+        }
     }
     if (o.meth_file.empty() && o.meth_file_test.empty()) {  // check_options (:299-303)
         std::cout << "FATAL  : no meth file provided! Please use the --meth-file option." << std::endl;

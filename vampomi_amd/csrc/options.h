@@ -42,6 +42,10 @@ struct Options {
     std::string meth_na = "pass";
     double meth_na_max_frac = 1.0;
     bool meth_na_max_frac_set = false;
+    // --cov-adjust none | residual: with residual the linear model's matrix and
+    // phenotype are replaced at ingest by their residuals on the intercept and
+    // the --C columns of --cov-file (--cov-file-test in --run-mode test)
+    std::string cov_adjust = "none";
 };
 
 // Parses argv exactly like Options::read_command_line_options + check_options:

@@ -296,6 +296,8 @@ extern "C" vampomi_status vampomi_vamp_begin(vampomi_ctx* c, const vampomi_param
     if (p->model && !probit && std::strcmp(p->model, "linear") != 0)  // src/vamp.cpp:98-104
         return fail(VAMPOMI_ERR_MODEL, std::string("Invalid model specification! ('") + p->model + "')");
     if (p->L < 1 || p->L > VAMPOMI_MAX_L) return fail(VAMPOMI_ERR_ARG, "number of mixture components out of range");
+    if (probit && c->adj_R)  // (the probit model fits its own covariates: vampomi_set_covariates)
+        return fail(VAMPOMI_ERR_STATE, "a covariate-adjusted context runs the linear model only");
     HIPCHK(hipSetDevice(c->device));
     STCHK(op_agree(c));  // several ranks: the one-pass / head-start choice, agreed here, where every rank is
     c->run.reset(new VampRun());
