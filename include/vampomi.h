@@ -197,6 +197,19 @@ vampomi_status vampomi_get_row_subset(const vampomi_ctx* ctx, int64_t* N_file, i
  * cannot be opened is VAMPOMI_ERR_IO. */
 vampomi_status vampomi_phen_rows(const char* phen_path, const char* keep_path, int drop_na, int64_t* rows,
                                  int64_t cap, int64_t* N_file, int64_t* n);
+/* The rows that an analysis of all T phenotype files keeps; needs no device.
+ * Every file must have the same number of rows and the same (FID, IID)
+ * sequence, else VAMPOMI_ERR_ARG (vampomi_last_error names the first
+ * differing file and row).  The keep file is vampomi_phen_rows's.  With
+ * drop_na != 0 a row is kept iff it is kept and not "NA" in EVERY file; with
+ * drop_na == 0 an "NA" in a kept row of any file is VAMPOMI_ERR_NAN_PHEN
+ * (the message names the file).  na_per_file (T entries, may be NULL): the
+ * "NA"s among the rows the keep file leaves, per file.  rows, cap, *N_file
+ * and *n as vampomi_phen_rows's; for T = 1 the call returns what
+ * vampomi_phen_rows returns. */
+vampomi_status vampomi_phen_rows_common(const char* const* phen_paths, int T, const char* keep_path, int drop_na,
+                                        int64_t* rows, int64_t cap, int64_t* N_file, int64_t* n,
+                                        int64_t* na_per_file);
 /* marker-major fp64 file (README.md:15): this shard's bytes [S*N*8, (S+M)*N*8).
  * On an F32 or U16 context each chunk is staged on the device as fp64 and
  * rounded (nearest even) or quantised (VAMPOMI_STORE_U16: range-checked,
@@ -545,6 +558,27 @@ vampomi_status vampomi_step_phases(vampomi_ctx* ctx, double* solve_s, double* st
 vampomi_status vampomi_assoc_loo(vampomi_ctx* ctx, const double* est, double* pvals, double* stats,
                                  int mem);
 vampomi_status vampomi_assoc_se(vampomi_ctx* ctx, const double* r1, double gam1, double* pvals, int mem);
+/* COLLECTIVE.  vampomi_assoc_loo for T >= 1 phenotypes against the resident
+ * shard; the context's own phenotype is neither needed nor touched.
+ * Y (host): T columns of N values, stride ldY >= N; each goes through what
+ * vampomi_set_phen does (the covariate projection of an adjusted context,
+ * then `standardize` as vampomi_set_phen's).  est: T x M, phenotype-major,
+ * in `mem`, each row this shard's slice of that phenotype's estimate file;
+ * NULL (on every rank) stands for all zeros, the plain marginal tests, and
+ * skips the A.x passes (y_mod = y exactly).  pvals (T x M) and stats
+ * (T x M x 5), in `mem`, may each be NULL.
+ * The phenotypes are served in chunks of up to four: per chunk ONE A.x pass
+ * with that many right-hand sides and ONE pass over the raw matrix that forms
+ * all their sums (a chunk of one uses vampomi_assoc_loo's own kernel), so T
+ * phenotypes read the matrix 2*ceil(T/4) times instead of 2*T.
+ * Block t of pvals and stats is, bit for bit, what vampomi_set_phen(ctx, Y_t,
+ * standardize) followed by vampomi_assoc_loo(ctx, est_t, ...) returns on the
+ * same context under the default association-pass variant, for every storage
+ * and on any number of ranks.  The pass is counted in vampomi_stats.loo
+ * (bytes of a chunk of KT: esize*N*M + 8*N*KT + 8*M*6*KT).
+ * VAMPOMI_ERR_ARG: T < 1, Y NULL, ldY < N; VAMPOMI_ERR_STATE: no matrix loaded. */
+vampomi_status vampomi_assoc_loo_multi(vampomi_ctx* ctx, int T, const double* Y, int64_t ldY, int standardize,
+                                       const double* est, double* pvals, double* stats, int mem);
 
 /* ---- --run-mode test (src/main_meth.cpp:112-205) ----
  * On a context holding the TEST data set (N = N_test, its own marker
@@ -634,7 +668,8 @@ vampomi_status vampomi_dev_read_ceiling(vampomi_ctx* ctx, int reps, double* us_m
 /* the kernel (as rocprofv3 names it) that pass `which` with K RHS launches now
  * (mode 1: the CG form, i.e. A^T.u with the lmmse_mult epilogue, A.x with the
  * fused direction update; which = 2: the association-test pass of
- * vampomi_assoc_loo) */
+ * vampomi_assoc_loo, or with K = 2, 3, 4 that of a chunk of K phenotypes of
+ * vampomi_assoc_loo_multi) */
 /* (an F32 / U16 context launches the narrow entry points: the same names with
  * an _f32 / _u16 suffix before the template arguments) */
 vampomi_status vampomi_dev_kernel_name(const vampomi_ctx* ctx, int which, int K, int mode, char* out, int cap);

@@ -24,7 +24,7 @@ from ._lib import (CLI_PATH, GEN_GAUSS, GEN_METH, LIB_PATH, MAX_L, MEM_DEVICE, M
                    STORE_F32, STORE_F64, STORE_U16, UNIQUE_ID_BYTES, Params, Result, ShardDesc, Stats, VampomiError,
                    check, load)
 
-__all__ = ["Data", "Vamp", "VampOptions", "divide_work", "comm_unique_id", "phen_rows", "adjust_basis", "VampomiError", "LIB_PATH", "CLI_PATH",
+__all__ = ["Data", "Vamp", "VampOptions", "divide_work", "comm_unique_id", "phen_rows", "phen_rows_common", "adjust_basis", "VampomiError", "LIB_PATH", "CLI_PATH",
            "GEN_GAUSS", "GEN_METH", "STORE_F64", "STORE_F32", "STORE_U16", "load"]
 
 _STORAGE = {"f64": STORE_F64, "f32": STORE_F32, "u16": STORE_U16}
@@ -64,6 +64,29 @@ def phen_rows(path: str, keep_file: Optional[str] = None, drop_na: bool = False)
     check(lib.vampomi_phen_rows(path.encode(), keep, 1 if drop_na else 0, _dp(rows), n.value, C.byref(nf),
                                 C.byref(n)))
     return rows[: n.value], nf.value
+
+
+def phen_rows_common(paths, keep_file: Optional[str] = None, drop_na: bool = False):
+    """(rows, N_file, na_per_file): the ascending rows that an analysis of all
+    the PLINK phenotype files ``paths`` keeps (vampomi_phen_rows_common; no
+    device needed).  The files must list the same individuals in the same
+    order (else status 1, the message naming the first differing file and
+    row).  ``keep_file`` as :func:`phen_rows`'s; with ``drop_na`` a row is kept
+    iff it is kept and not ``NA`` in every file, else an ``NA`` in a kept row
+    of any file raises status 5 naming the file.  ``na_per_file``: the ``NA``
+    count of each file among the rows the keep file leaves."""
+    lib = load()
+    paths = [str(p) for p in paths]
+    arr = (C.c_char_p * max(len(paths), 1))(*[p.encode() for p in paths])
+    keep = None if keep_file is None else str(keep_file).encode()
+    nf, n = C.c_int64(), C.c_int64()
+    na = np.zeros(max(len(paths), 1), dtype=np.int64)
+    check(lib.vampomi_phen_rows_common(arr, len(paths), keep, 1 if drop_na else 0, None, 0, C.byref(nf), C.byref(n),
+                                       _dp(na)))
+    rows = np.zeros(max(n.value, 1), dtype=np.int64)
+    check(lib.vampomi_phen_rows_common(arr, len(paths), keep, 1 if drop_na else 0, _dp(rows), n.value, C.byref(nf),
+                                       C.byref(n), _dp(na)))
+    return rows[: n.value], nf.value, na[: len(paths)]
 
 
 def adjust_basis(Z: np.ndarray):
@@ -456,6 +479,30 @@ class Data:
         st = np.zeros((max(self.M, 1), 5))
         check(self._lib.vampomi_assoc_loo(self.ctx, _dp(est), _dp(pv), _dp(st), MEM_HOST))
         return pv[: self.M], st[: self.M]
+
+    def assoc_loo_multi(self, Y: np.ndarray, est: Optional[np.ndarray] = None, standardize: bool = True):
+        """:meth:`assoc_loo` for T phenotypes with the matrix read once per
+        four of them (vampomi_assoc_loo_multi).  Y: (T, N), one phenotype per
+        row, each prepared as :meth:`set_phen` prepares it; the context's own
+        phenotype is not touched.  est: (T, M) estimate-file slices, or None
+        for the plain marginal tests (no A.x pass).  COLLECTIVE.  Returns
+        (pvals (T, M), stats (T, M, 5)); block t equals, bit for bit,
+        ``set_phen(Y[t], standardize)`` followed by ``assoc_loo(est[t])``."""
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim != 2 or Y.shape[1] != self.N:
+            raise ValueError("Y must be (T, N)")
+        T = Y.shape[0]
+        if est is not None:
+            est = np.ascontiguousarray(est, dtype=np.float64)
+            if est.shape != (T, self.M):
+                raise ValueError("estimates must be (T, M)")
+            if est.size == 0:  # an empty shard still takes part in the A.x: a non-null pointer
+                est = np.zeros(1)
+        pv = np.zeros((T, max(self.M, 1)))
+        st = np.zeros((T, max(self.M, 1), 5))
+        check(self._lib.vampomi_assoc_loo_multi(self.ctx, T, _dp(Y), self.N, 1 if standardize else 0,
+                                                None if est is None else _dp(est), _dp(pv), _dp(st), MEM_HOST))
+        return pv[:, : self.M], st[:, : self.M]
 
     def assoc_se(self, r1: np.ndarray, gam1: float) -> np.ndarray:
         """--pval-method se (src/main_meth.cpp:218-242)."""

@@ -115,6 +115,8 @@ SIGNATURES = {
     "vampomi_get_row_subset": (C.c_int, [_P, C.POINTER(C.c_int64), _P]),
     "vampomi_phen_rows": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64),
                                     C.POINTER(C.c_int64)]),
+    "vampomi_phen_rows_common": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.c_int, _P, C.c_int64,
+                                           C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
     "vampomi_load_meth_file": (C.c_int, [_P, C.c_char_p]),
     "vampomi_load_meth_file_f32": (C.c_int, [_P, C.c_char_p]),
     "vampomi_load_meth_host": (C.c_int, [_P, _P, C.c_int64]),
@@ -146,6 +148,7 @@ SIGNATURES = {
     "vampomi_test_metrics": (C.c_int, [_P, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]),
     "vampomi_assoc_loo": (C.c_int, [_P, _P, _P, _P, C.c_int]),
     "vampomi_assoc_se": (C.c_int, [_P, _P, C.c_double, _P, C.c_int]),
+    "vampomi_assoc_loo_multi": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, _P, _P, _P, C.c_int]),
     "vampomi_update_prior": (C.c_int, [_P, _P, C.c_double, C.POINTER(C.c_int), _P, _P, C.c_int, C.c_double,
                                         C.c_int, C.c_double, C.c_int]),
     "vampomi_denoise_bin": (C.c_int, [_P, _P, C.c_double, _P, C.POINTER(C.c_double), C.c_int]),

@@ -198,6 +198,11 @@ struct vampomi_ctx {
     unsigned long long* op_ts = nullptr;  // VAMPOMI_OP_TS=1 (TM_TS builds): the last launch's workgroup times
     double* nbuf = nullptr;     // kMaxRhs * ld scratch N-vectors (API calls)
     double* mbuf = nullptr;     // (2*kMaxRhs) * M scratch M-vectors (API calls)
+    // vampomi_assoc_loo_multi's chunk scratch (allocated on first use): am_n,
+    // 2 * kLooMultiMax ld-vectors (y_t, then ymod_t); am_m, 8 * kLooMultiMax
+    // M-vectors (estimates, x1, p-values, then the 5 sums of each phenotype)
+    double* am_n = nullptr;
+    double* am_m = nullptr;
 
     bool timing = false;
     int tperiod = 1;            // time 1 in tperiod launches of each (class, K)

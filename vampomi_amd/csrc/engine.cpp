@@ -1136,7 +1136,7 @@ void release_ctx_resources(vampomi_ctx* c) {
     if (c->na_cnt) (void)hipFree(c->na_cnt);
     c->na_cnt = nullptr;
     for (double** p : {&c->mave, &c->msig, &c->y, &c->ax_part, &c->red_part, &c->scal, &c->nbuf, &c->mbuf,
-                       &c->op_part, &c->op_nvec, &c->cov_Z, &c->cov_part, &c->cov_dev})
+                       &c->op_part, &c->op_nvec, &c->cov_Z, &c->cov_part, &c->cov_dev, &c->am_n, &c->am_m})
         dev_free(*p);
     if (c->op_xg) (void)hipFree(c->op_xg);
     c->op_xg = nullptr;
@@ -2081,6 +2081,37 @@ extern "C" vampomi_status vampomi_phen_rows(const char* phen_path, const char* k
     return VAMPOMI_OK;
 }
 
+// the rows that an analysis of all T phenotype files keeps: the files must
+// list the same individuals in the same order; vampomi_phen_rows per file,
+// intersected (vio::phen_rows_common)
+extern "C" vampomi_status vampomi_phen_rows_common(const char* const* phen_paths, int T, const char* keep_path,
+                                                   int drop_na, int64_t* rows, int64_t cap, int64_t* N_file,
+                                                   int64_t* n, int64_t* na_per_file) {
+    if (!phen_paths || T < 1) return fail(VAMPOMI_ERR_ARG, "no phenotype files");
+    for (int t = 0; t < T; ++t)
+        if (!phen_paths[t]) return fail(VAMPOMI_ERR_ARG, "null argument");
+    std::vector<int64_t> kept, nas;
+    int64_t nfile = 0;
+    std::string err;
+    switch (vio::phen_rows_common(std::vector<std::string>(phen_paths, phen_paths + T), keep_path ? keep_path : "",
+                                  drop_na != 0, kept, &nfile, nullptr, &nas, nullptr, &err)) {
+        case 0: break;
+        case -1: return fail(VAMPOMI_ERR_IO, err);
+        case -2: return fail(VAMPOMI_ERR_NAN_PHEN, err);
+        default: return fail(VAMPOMI_ERR_ARG, err);
+    }
+    if (na_per_file) std::copy(nas.begin(), nas.end(), na_per_file);
+    if (N_file) *N_file = nfile;
+    if (n) *n = (int64_t)kept.size();
+    if (rows) {
+        if (cap < (int64_t)kept.size())
+            return fail(VAMPOMI_ERR_ARG, "rows holds " + std::to_string(cap) + " entries, " +
+                                             std::to_string(kept.size()) + " rows are kept");
+        std::copy(kept.begin(), kept.end(), rows);
+    }
+    return VAMPOMI_OK;
+}
+
 extern "C" vampomi_status vampomi_get_marker_stats(vampomi_ctx* c, double* mave, double* msig) {
     if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
     if (!c->have_X) return fail(VAMPOMI_ERR_STATE, "no methylation data loaded");
@@ -2378,6 +2409,94 @@ extern "C" vampomi_status vampomi_assoc_loo(vampomi_ctx* c, const double* est, d
     HIPCHK(vk::loo_pvals(M, st, (int)N, pv, c->st));
     if (stats) STCHK(stage_out(c, st, 5 * M, mem, stats));
     if (pvals) STCHK(stage_out(c, pv, M, mem, pvals));
+    STCHK(sync_stream(c, c->st));
+    if (c->timing) resolve_timing(c);
+    return VAMPOMI_OK;
+}
+
+// vampomi_assoc_loo for T phenotypes with the shard read once per chunk of up
+// to vk::kLooMultiMax of them: per chunk one batched A.x
+// (none with est == NULL), ymod_t = y_t - z_t, one vk::loo_multi_sums (a chunk
+// of one: vk::loo_sums), the p-values of the chunk's blocks.  Block t is bit
+// for bit vampomi_set_phen(Y_t) + vampomi_assoc_loo(est_t) under the default
+// association variant.  COLLECTIVE (one A.x per chunk; est is NULL on every
+// rank or on none).
+extern "C" vampomi_status vampomi_assoc_loo_multi(vampomi_ctx* c, int T, const double* Y, int64_t ldY,
+                                                  int standardize, const double* est, double* pvals, double* stats,
+                                                  int mem) {
+    CollScope cs_(c);
+    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
+    if (T < 1) return fail(VAMPOMI_ERR_ARG, "assoc_loo_multi: T < 1");
+    if (!Y) return fail(VAMPOMI_ERR_ARG, "assoc_loo_multi: null Y");
+    if (ldY < c->N) return fail(VAMPOMI_ERR_ARG, "assoc_loo_multi: ldY < N");
+    if (!c->have_X) return fail(VAMPOMI_ERR_STATE, "load methylation data first");
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t M = c->M, N = c->N, Mx = std::max<int64_t>(M, 1), ld = c->ld;
+    constexpr int KM = vk::kLooMultiMax;
+    if (!c->am_n) {
+        STCHK(dev_alloc(&c->am_n, (size_t)2 * KM * ld));
+        HIPCHK(hipMemsetAsync(c->am_n, 0, (size_t)2 * KM * ld * 8, c->st));  // pad rows stay zero
+    }
+    if (!c->am_m) STCHK(dev_alloc(&c->am_m, (size_t)8 * KM * Mx));
+    double* yd = c->am_n;                  // y_t
+    double* ymod = c->am_n + KM * ld;      // y_t - z_t
+    double* e = c->am_m;                   // estimate-file values
+    double* x1 = c->am_m + KM * Mx;        // x1_hat * sqrt(N)
+    double* pv = c->am_m + 2 * KM * Mx;    // p-values
+    double* st = c->am_m + 3 * KM * Mx;    // KT blocks of 5 sums per marker
+    double* z = c->nbuf;                   // A x1_t
+    // every column as vampomi_set_phen prepares it (host; the context's own
+    // phenotype is not touched)
+    std::vector<double> yh((size_t)T * (size_t)N), col;
+    for (int t = 0; t < T; ++t) {
+        col.assign(Y + (int64_t)t * ldY, Y + (int64_t)t * ldY + N);
+        adjust_phen(c, col);
+        if (standardize) vio::standardize_phen(col);
+        std::copy(col.begin(), col.end(), yh.begin() + (size_t)t * (size_t)N);
+    }
+    const double sqrtN = std::sqrt((double)N);
+    for (int t0 = 0; t0 < T; t0 += KM) {
+        const int KT = std::min(KM, T - t0);
+        double* ym = est ? ymod : yd;  // without estimates ymod_t = y_t
+        for (int k = 0; k < KT; ++k)
+            HIPCHK(hipMemcpyAsync(yd + (int64_t)k * ld, yh.data() + (size_t)(t0 + k) * (size_t)N, (size_t)N * 8,
+                                  hipMemcpyHostToDevice, c->st));
+        if (est) {
+            const double* xs[KM] = {};
+            for (int k = 0; k < KT; ++k) {
+                STCHK(stage_in(c, est + (int64_t)(t0 + k) * M, M, mem, e + k * Mx));
+                HIPCHK(vk::mul_scalar(M, e + k * Mx, sqrtN, x1 + k * Mx, c->st));
+                xs[k] = x1 + k * Mx;
+            }
+            STCHK(ax_dev(c, KT, xs, z));
+            for (int k = 0; k < KT; ++k)
+                HIPCHK(vk::axpby(N, 1.0, yd + (int64_t)k * ld, -1.0, z + (int64_t)k * ld, ymod + (int64_t)k * ld, c->st));
+        } else {
+            HIPCHK(hipMemsetAsync(x1, 0, (size_t)KT * Mx * 8, c->st));
+        }
+        if (KT == 1) {
+            TimedLaunch tl = launch_stat(c, 2, 1,
+                                         (double)c->esize() * (double)N * (double)M + 8.0 * (double)N + 8.0 * 6.0 * (double)M,
+                                         11.0 * (double)N * (double)M);
+            HIPCHK(vk::loo_sums(c->shard(), ym, x1, sqrtN, st, c->st, c->loo_variant, vk::Timing{tl.a, tl.b}));
+        } else {
+            // raw X once, KT ymod and x1 vectors, KT blocks of sums; per element
+            // 4 operations for the quotient and the x-only sums, 7 per phenotype.
+            // (Every width is booked into the one stats.loo record, which has
+            // no per-K records: its time is exact at timing period 1 only.  At
+            // a longer period it is the sampled mean times the launch count
+            // over launches of different widths and costs, so it is biased)
+            TimedLaunch tl = launch_stat(c, 2, KT,
+                                         (double)c->esize() * (double)N * (double)M + 8.0 * (double)N * KT +
+                                             8.0 * 6.0 * (double)M * KT,
+                                         (4.0 + 7.0 * KT) * (double)N * (double)M);
+            HIPCHK(vk::loo_multi_sums(c->shard(), KT, ym, x1, sqrtN, st, c->st, vk::Timing{tl.a, tl.b}));
+        }
+        c->stats.a_passes_exec++;
+        HIPCHK(vk::loo_pvals((int64_t)KT * M, st, (int)N, pv, c->st));
+        if (stats) STCHK(stage_out(c, st, 5 * M * KT, mem, stats + (int64_t)t0 * 5 * M));
+        if (pvals) STCHK(stage_out(c, pv, M * KT, mem, pvals + (int64_t)t0 * M));
+    }
     STCHK(sync_stream(c, c->st));
     if (c->timing) resolve_timing(c);
     return VAMPOMI_OK;
@@ -2809,7 +2928,9 @@ extern "C" vampomi_status vampomi_dev_kernel_name(const vampomi_ctx* c, int whic
     if (!c || !out || cap < 1) return fail(VAMPOMI_ERR_ARG, "bad argument");
     // which = 3: mode carries N (the operator's instantiation depends on it)
     const int ek = c->ek();  // the element kind: the suffix of the entry points
-    const std::string n = which == 2   ? vk::loo_kernel_name(c->loo_variant, ek)
+    // which = 2: K >= 2 names the pass of a chunk of K phenotypes (vampomi_assoc_loo_multi)
+    const std::string n = which == 2 && K >= 2 && K <= vk::kLooMultiMax ? vk::loo_multi_kernel_name(K, ek)
+                          : which == 2 ? vk::loo_kernel_name(c->loo_variant, ek)
                           : which == 3 ? op_name(c, K)
                           : which == 0 ? vk::ax_kernel_name(K, mode == 1, c->axp, ek)
                                        : vk::kernel_name(1, K, mode, c->atx_variant, ek);

@@ -4,6 +4,7 @@
 #include <fcntl.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstdio>
@@ -11,6 +12,7 @@
 #include <cstring>
 #include <chrono>
 #include <fstream>
+#include <iterator>
 #include <map>
 #include <set>
 #include <thread>
@@ -77,15 +79,13 @@ bool read_phen_table(const std::string& path, PhenTable& t) {
     return true;
 }
 
-int phen_rows(const std::string& phen_path, const std::string& keep_path, bool drop_na, std::vector<int64_t>& rows,
-              int64_t* N_file, int64_t* not_kept, int64_t* na_dropped, std::string* err) {
-    PhenTable t;
-    if (!read_phen_table(phen_path, t)) {
-        *err = "FATAL: could not open phenotype file: " + phen_path;
-        return -1;
-    }
+// named[i]: the keep file names row i of t (all rows without a keep file).
+// 0, or phen_rows' -1 / -3
+static int keep_mask(const PhenTable& t, const std::string& phen_path, const std::string& keep_path,
+                     std::vector<char>& named, std::string* err) {
     typedef std::pair<std::string, std::string> Id;
     std::map<Id, int64_t> keep;  // the pair and the first line that names it
+    named.assign(t.value.size(), 1);
     if (!keep_path.empty()) {
         std::ifstream in(keep_path);
         if (!in.is_open()) {
@@ -117,15 +117,19 @@ int phen_rows(const std::string& phen_path, const std::string& keep_path, bool d
                    missing->first.first + " " + missing->first.second + "\" in phenotype file " + phen_path;
             return -3;
         }
+        for (size_t i = 0; i < t.value.size(); ++i) named[i] = keep.count(Id(t.fid[i], t.iid[i])) ? 1 : 0;
     }
+    return 0;
+}
+
+// the named rows without an "NA", ascending.  0, or phen_rows' -2
+static int rows_of(const std::vector<char>& named, const std::vector<char>& na, bool drop_na,
+                   std::vector<int64_t>& rows, int64_t* na_dropped, std::string* err) {
     rows.clear();
-    int64_t out = 0, nas = 0;
-    for (size_t i = 0; i < t.value.size(); ++i) {
-        if (!keep_path.empty() && !keep.count(Id(t.fid[i], t.iid[i]))) {
-            ++out;
-            continue;
-        }
-        if (t.na[i]) {
+    int64_t nas = 0;
+    for (size_t i = 0; i < named.size(); ++i) {
+        if (!named[i]) continue;
+        if (na[i]) {
             if (!drop_na) {
                 *err = "NAN in data!";
                 return -2;
@@ -135,9 +139,73 @@ int phen_rows(const std::string& phen_path, const std::string& keep_path, bool d
         }
         rows.push_back((int64_t)i);
     }
-    if (N_file) *N_file = (int64_t)t.value.size();
-    if (not_kept) *not_kept = out;
     if (na_dropped) *na_dropped = nas;
+    return 0;
+}
+
+int phen_rows(const std::string& phen_path, const std::string& keep_path, bool drop_na, std::vector<int64_t>& rows,
+              int64_t* N_file, int64_t* not_kept, int64_t* na_dropped, std::string* err) {
+    PhenTable t;
+    if (!read_phen_table(phen_path, t)) {
+        *err = "FATAL: could not open phenotype file: " + phen_path;
+        return -1;
+    }
+    std::vector<char> named;
+    if (const int rc = keep_mask(t, phen_path, keep_path, named, err)) return rc;
+    if (const int rc = rows_of(named, t.na, drop_na, rows, na_dropped, err)) return rc;
+    if (N_file) *N_file = (int64_t)t.value.size();
+    if (not_kept) *not_kept = (int64_t)std::count(named.begin(), named.end(), (char)0);
+    return 0;
+}
+
+int phen_rows_common(const std::vector<std::string>& phen_paths, const std::string& keep_path, bool drop_na,
+                     std::vector<int64_t>& rows, int64_t* N_file, int64_t* not_kept,
+                     std::vector<int64_t>* na_per_file, std::vector<std::vector<double>>* values, std::string* err) {
+    const size_t T = phen_paths.size();
+    PhenTable first;
+    std::vector<std::vector<char>> na(T);
+    if (values) values->assign(T, std::vector<double>());
+    for (size_t t = 0; t < T; ++t) {  // every file once: its values and NA flags, its IDs held against the first's
+        PhenTable cur;
+        PhenTable& tab = t == 0 ? first : cur;
+        if (!read_phen_table(phen_paths[t], tab)) {
+            *err = "FATAL: could not open phenotype file: " + phen_paths[t];
+            return -1;
+        }
+        if (t > 0 && cur.value.size() != first.value.size()) {
+            *err = "phenotype file " + phen_paths[t] + " has " + std::to_string(cur.value.size()) + " rows, " +
+                   phen_paths[0] + " has " + std::to_string(first.value.size());
+            return -3;
+        }
+        for (size_t i = 0; t > 0 && i < cur.value.size(); ++i)
+            if (cur.fid[i] != first.fid[i] || cur.iid[i] != first.iid[i]) {
+                *err = "phenotype file " + phen_paths[t] + ", row " + std::to_string(i + 1) + ": individual \"" +
+                       cur.fid[i] + " " + cur.iid[i] + "\" where " + phen_paths[0] + " has \"" + first.fid[i] + " " +
+                       first.iid[i] + "\"";
+                return -3;
+            }
+        na[t] = tab.na;
+        if (values) (*values)[t] = tab.value;
+    }
+    std::vector<char> named;  // (the same individuals in every file: one mask)
+    if (const int rc = keep_mask(first, phen_paths[0], keep_path, named, err)) return rc;
+    if (na_per_file) na_per_file->assign(T, 0);
+    std::vector<int64_t> cur, both;
+    for (size_t t = 0; t < T; ++t) {
+        if (const int rc = rows_of(named, na[t], drop_na, cur, na_per_file ? &(*na_per_file)[t] : nullptr, err)) {
+            if (T > 1) *err += " (phenotype file " + phen_paths[t] + ")";
+            return rc;
+        }
+        if (t == 0) {
+            rows.swap(cur);
+        } else {
+            both.clear();
+            std::set_intersection(rows.begin(), rows.end(), cur.begin(), cur.end(), std::back_inserter(both));
+            rows.swap(both);
+        }
+    }
+    if (N_file) *N_file = (int64_t)first.value.size();
+    if (not_kept) *not_kept = (int64_t)std::count(named.begin(), named.end(), (char)0);
     return 0;
 }
 

@@ -33,6 +33,15 @@ bool read_phen_table(const std::string& path, PhenTable& t);
 // rows the keep file and the "NA"s took out (each may be null).
 int phen_rows(const std::string& phen_path, const std::string& keep_path, bool drop_na, std::vector<int64_t>& rows,
               int64_t* N_file, int64_t* not_kept, int64_t* na_dropped, std::string* err);
+// The rows that an analysis of all the phenotype files keeps: phen_rows per
+// file, intersected, each file parsed once.  The files must have the same
+// number of rows and the same (FID, IID) sequence, else -3 naming the first
+// differing file and row; a -2 names the file when there are several.
+// *na_per_file: the "NA"s in each file's rows that the keep file names;
+// *values: each file's values, all its rows ("NA" as 0) (each may be null).
+int phen_rows_common(const std::vector<std::string>& phen_paths, const std::string& keep_path, bool drop_na,
+                     std::vector<int64_t>& rows, int64_t* N_file, int64_t* not_kept,
+                     std::vector<int64_t>* na_per_file, std::vector<std::vector<double>>* values, std::string* err);
 
 // data::read_covariates (src/data.cpp:159-227): a header line, then per row
 // two IDs and exactly C numeric fields, split like read_phen's.  out: C

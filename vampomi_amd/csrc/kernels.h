@@ -604,6 +604,17 @@ hipError_t cov_offset(int64_t N, int C, const double* Z, int64_t ld, const doubl
 // samples of marker j (RAW X), ym = ymod + X / sqrtN * x1[j]  (data::pvals_loo)
 hipError_t loo_sums(const Shard& s, const double* ymod, const double* x1, double sqrtN, double* stats,
                     hipStream_t st, int variant = kLooDefault, const Timing& tm = Timing{});
+// The same sums for KT = 2, 3, 4 phenotypes from one pass over the shard:
+// ymod: KT ld-padded vectors of stride s.ld, x1: KT vectors of stride
+// max(M, 1), stats: KT blocks of 5*M.  Block t holds, bit for bit, what
+// loo_sums(s, ymod_t, x1_t, ...) gives under any 8-wave workgroup variant
+// (kLooDefault among them).  Markers per workgroup and unroll per KT (they do
+// not change the bits; profiles/assoc_multi.md):
+constexpr int kLooMultiMax = 4;
+constexpr int kLooMultiG2 = 4, kLooMultiUJ2 = 2, kLooMultiG3 = 4, kLooMultiUJ3 = 1, kLooMultiG4 = 2, kLooMultiUJ4 = 2;
+hipError_t loo_multi_sums(const Shard& s, int KT, const double* ymod, const double* x1, double sqrtN, double* stats,
+                          hipStream_t st, const Timing& tm = Timing{});
+std::string loo_multi_kernel_name(int KT, int ek = 0);
 std::string loo_kernel_name(int variant, int ek = 0);
 int loo_variant_count();
 bool loo_variant_ok(int v);

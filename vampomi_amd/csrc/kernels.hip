@@ -3760,6 +3760,178 @@ hipError_t loo_sums(const Shard& s, const double* ymod, const double* x1, double
     return hipGetLastError();
 }
 
+// The sums of KT phenotypes from ONE pass over the shard:
+// loo_wg_body at W = 8 with the x-only work of an element (the corrected
+// quotient q, sum X, sum X^2) done once and the three phenotype sums done KT
+// times.  Rows, per-lane order, wave_sum and the wave-order LDS sum are
+// loo_wg_body's, and the per-phenotype expressions are its own, so block t of
+// stats is bit for bit what loo_wg_kernel<*, *, 8> gives for (ymod_t, x1_t).
+// acc[g][0..1]: sum X, sum X^2 (written into every block); acc[g][2 + 3t ..]:
+// sum X*ym_t, sum ym_t, sum ym_t^2.
+// ymod: KT vectors of stride ldy; x1: KT vectors of stride Mx; stats: KT
+// blocks of 5*M.
+template <int KT, int G, int UJ, int W, class XE>
+__device__ __forceinline__ void loo_multi_body(const XE* __restrict__ X, int64_t ld, int64_t N, int64_t M,
+                                               const double* __restrict__ ymod, int64_t ldy,
+                                               const double* __restrict__ x1, int64_t Mx, double sqrtN,
+                                               double* __restrict__ stats) {
+    constexpr int NA = 2 + 3 * KT;  // accumulators per marker
+    __shared__ double part[W][NA * G];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t m0 = (int64_t)blockIdx.x * G;
+    const double rinv = 1.0 / sqrtN;
+    double acc[G][NA];
+    double xj[G][KT];
+    const XE* col[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const int64_t m = (m0 + g < M) ? m0 + g : M - 1;  // clamp: in-bounds, discarded
+#pragma unroll
+        for (int t = 0; t < KT; ++t) xj[g][t] = x1[(int64_t)t * Mx + m];
+        col[g] = X + m * ld;
+#pragma unroll
+        for (int q = 0; q < NA; ++q) acc[g][q] = 0.0;
+    }
+    auto add = [&](int g, double m, const double (&y)[KT]) {
+        const double q0 = m * rinv;
+        const double q = __builtin_fma(__builtin_fma(-q0, sqrtN, m), rinv, q0);
+        acc[g][0] += m;
+        acc[g][1] += m * m;
+#pragma unroll
+        for (int t = 0; t < KT; ++t) {
+            const double ym = y[t] + q * xj[g][t];
+            acc[g][2 + 3 * t] += m * ym;
+            acc[g][3 + 3 * t] += ym;
+            acc[g][4 + 3 * t] += ym * ym;
+        }
+    };
+    constexpr int64_t RS = 128 * W;  // rows per load round of the workgroup
+    int64_t j = 2 * lane + 128 * wave;
+    for (; j + RS * (UJ - 1) < N; j += RS * UJ) {
+        xpair_t<XE> xx[UJ][G];
+#pragma unroll
+        for (int u = 0; u < UJ; ++u)
+#pragma unroll
+            for (int g = 0; g < G; ++g) xx[u][g] = ldx<true>(col[g] + j + RS * u);
+#pragma unroll
+        for (int u = 0; u < UJ; ++u) {
+            double ya[KT], yb[KT];
+#pragma unroll
+            for (int t = 0; t < KT; ++t) {
+                const v2d yy = ld2(ymod + (int64_t)t * ldy + j + RS * u);
+                ya[t] = yy.x;
+                yb[t] = yy.y;
+            }
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                add(g, widen(xx[u][g]).x, ya);
+                add(g, widen(xx[u][g]).y, yb);
+            }
+        }
+    }
+    for (; j < N; j += RS) {  // (N even or the pad row: ld-padded columns, zero pads)
+        xpair_t<XE> xx[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) xx[g] = ldx<true>(col[g] + j);
+        double ya[KT], yb[KT];
+#pragma unroll
+        for (int t = 0; t < KT; ++t) {
+            const v2d yy = ld2(ymod + (int64_t)t * ldy + j);
+            ya[t] = yy.x;
+            yb[t] = yy.y;
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            add(g, widen(xx[g]).x, ya);
+            add(g, widen(xx[g]).y, yb);
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+        for (int q = 0; q < NA; ++q) {
+            const double s = wave_sum(acc[g][q]);
+            if (lane == 0) part[wave][NA * g + q] = s;
+        }
+    __syncthreads();
+    // thread i < 5*KT*G: phenotype t, marker g, sum q of block t
+    const int i = (int)threadIdx.x;
+    if (i < 5 * KT * G) {
+        const int t = i / (5 * G), g = (i % (5 * G)) / 5, q = i % 5;
+        if (m0 + g < M) {
+            const int src = NA * g + (q < 2 ? q : q + 3 * t);
+            double s = 0.0;
+#pragma unroll
+            for (int w = 0; w < W; ++w) s += part[w][src];
+            stats[(int64_t)t * 5 * M + 5 * (m0 + g) + q] = s;
+        }
+    }
+}
+
+template <int KT, int G, int UJ, int W>
+__global__ __launch_bounds__(64 * W) void loo_multi_kernel(const double* __restrict__ X, int64_t ld, int64_t N,
+                                                           int64_t M, const double* __restrict__ ymod, int64_t ldy,
+                                                           const double* __restrict__ x1, int64_t Mx, double sqrtN,
+                                                           double* __restrict__ stats) {
+    loo_multi_body<KT, G, UJ, W>(X, ld, N, M, ymod, ldy, x1, Mx, sqrtN, stats);
+}
+
+template <int KT, int G, int UJ, int W>
+__global__ __launch_bounds__(64 * W) void loo_multi_kernel_f32(const float* __restrict__ X, int64_t ld, int64_t N,
+                                                               int64_t M, const double* __restrict__ ymod,
+                                                               int64_t ldy, const double* __restrict__ x1, int64_t Mx,
+                                                               double sqrtN, double* __restrict__ stats) {
+    loo_multi_body<KT, G, UJ, W>(X, ld, N, M, ymod, ldy, x1, Mx, sqrtN, stats);
+}
+
+template <int KT, int G, int UJ, int W>
+__global__ __launch_bounds__(64 * W) void loo_multi_kernel_u16(const uint16_t* __restrict__ X, int64_t ld, int64_t N,
+                                                               int64_t M, const double* __restrict__ ymod,
+                                                               int64_t ldy, const double* __restrict__ x1, int64_t Mx,
+                                                               double sqrtN, double* __restrict__ stats) {
+    loo_multi_body<KT, G, UJ, W>(X, ld, N, M, ymod, ldy, x1, Mx, sqrtN, stats);
+}
+
+template <int KT, int G, int UJ>
+static void launch_loo_multi(const Shard& s, const double* ymod, const double* x1, double sqrtN, double* stats,
+                             hipStream_t st, const Timing& tm) {
+    const int64_t Mx = s.M > 1 ? s.M : 1;
+    const dim3 grid((unsigned)cdiv(s.M, G)), block(64 * 8);
+    if (s.u16)
+        hipExtLaunchKernelGGL((loo_multi_kernel_u16<KT, G, UJ, 8>), grid, block, 0, st, tm.start, tm.stop, 0, s.x16(),
+                              s.ld, s.N, s.M, ymod, s.ld, x1, Mx, sqrtN, stats);
+    else if (s.f32)
+        hipExtLaunchKernelGGL((loo_multi_kernel_f32<KT, G, UJ, 8>), grid, block, 0, st, tm.start, tm.stop, 0, s.x32(),
+                              s.ld, s.N, s.M, ymod, s.ld, x1, Mx, sqrtN, stats);
+    else
+        hipExtLaunchKernelGGL((loo_multi_kernel<KT, G, UJ, 8>), grid, block, 0, st, tm.start, tm.stop, 0, s.x64(),
+                              s.ld, s.N, s.M, ymod, s.ld, x1, Mx, sqrtN, stats);
+}
+
+std::string loo_multi_kernel_name(int KT, int ek) {
+    const int G = KT == 2 ? kLooMultiG2 : KT == 3 ? kLooMultiG3 : kLooMultiG4;
+    const int UJ = KT == 2 ? kLooMultiUJ2 : KT == 3 ? kLooMultiUJ3 : kLooMultiUJ4;
+    char b[64];
+    std::snprintf(b, sizeof b, "loo_multi_kernel%s<%d, %d, %d, 8>", xe_suffix(ek), KT, G, UJ);
+    return b;
+}
+
+// G and UJ per KT (kernels.h): the fastest of the scratch-free choices timed
+// at the C5 shard on MI355X, <2: 4, 2>, <3: 4, 1>, <4: 2, 2> against
+// <2: 2, 4 | 4, 1>, <3: 2, 2 | 4, 2>, <4: 4, 1 | 4, 2> (profiles/assoc_multi.md);
+// they do not change the bits
+hipError_t loo_multi_sums(const Shard& s, int KT, const double* ymod, const double* x1, double sqrtN, double* stats,
+                          hipStream_t st, const Timing& tm) {
+    if (s.M <= 0) return hipSuccess;
+    switch (KT) {
+        case 2: launch_loo_multi<2, kLooMultiG2, kLooMultiUJ2>(s, ymod, x1, sqrtN, stats, st, tm); break;
+        case 3: launch_loo_multi<3, kLooMultiG3, kLooMultiUJ3>(s, ymod, x1, sqrtN, stats, st, tm); break;
+        case 4: launch_loo_multi<4, kLooMultiG4, kLooMultiUJ4>(s, ymod, x1, sqrtN, stats, st, tm); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 // ln B(a, 1/2) and the Student-t upper tail: the same operations as the
 // oracle's orc_lnbeta_half / ibeta_cf / orc_t_sf (oracle/vamp_oracle.c),
 // standing for Boost's complemented students_t cdf (src/utilities.cpp:278-279)

@@ -17,6 +17,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <sstream>
 #include <string>
 #include <thread>
 #include <vector>
@@ -107,6 +108,73 @@ static int association_test(vampomi_ctx* ctx, const vopt::Options& opt, int rank
     return 0;
 }
 
+// --trait-file: one phenotype per non-blank, non-# line, "<name> <phen-file>
+// <estimate-file>".  False with *err set: a line without three fields, a
+// duplicate name, an estimate name without a parsable it_K, no line at all
+struct Trait {
+    std::string name, phen, est, it_str;
+};
+static bool read_traits(const std::string& path, std::vector<Trait>& traits, std::string* err) {
+    std::ifstream in(path);
+    if (!in.is_open()) {
+        *err = "could not open trait file: " + path;
+        return false;
+    }
+    std::string line;
+    for (int64_t lineno = 1; std::getline(in, line); ++lineno) {
+        std::istringstream ls(line);
+        std::vector<std::string> tok;
+        for (std::string w; ls >> w;) tok.push_back(w);
+        if (tok.empty() || tok[0][0] == '#') continue;
+        const std::string where = "trait file " + path + ", line " + std::to_string(lineno) + ": ";
+        if (tok.size() != 3) {
+            *err = where + "expected <name> <phen-file> <estimate-file>, found " + std::to_string(tok.size()) +
+                   (tok.size() == 1 ? " field" : " fields");
+            return false;
+        }
+        Trait t{tok[0], tok[1], tok[2], ""};
+        for (const Trait& o : traits)
+            if (o.name == t.name) {
+                *err = where + "duplicate name \"" + t.name + "\"";
+                return false;
+            }
+        if (!iteration_of(t.est, t.it_str)) {
+            *err = where + "cannot parse the iteration from estimate file \"" + t.est + "\"";
+            return false;
+        }
+        traits.push_back(t);
+    }
+    if (traits.empty()) {
+        *err = "trait file " + path + " names no phenotype";
+        return false;
+    }
+    return true;
+}
+
+// --run-mode association_test --pval-method loo --trait-file: every trait's
+// p-values from one load of the matrix (vampomi_assoc_loo_multi), each to the
+// file a single run with --out-name <name> writes.  Y: T columns of n;
+// standardize: as the single run's phenotype (raw 0/1 for --model bin_class)
+static int association_test_traits(vampomi_ctx* ctx, const vopt::Options& opt, const std::vector<Trait>& traits,
+                                   const std::vector<double>& Y, int64_t n, int standardize, int rank, int64_t M,
+                                   int64_t S) {
+    const size_t T = traits.size(), Mx = (size_t)std::max<int64_t>(M, 1);
+    std::vector<double> est(T * Mx, 0.0), pvals(T * Mx, 0.0);
+    for (size_t t = 0; t < T; ++t) vio::read_vec(traits[t].est, est.data() + t * (size_t)M, S, M);
+    if (vampomi_assoc_loo_multi(ctx, (int)T, Y.data(), n, standardize, est.data(), pvals.data(), nullptr,
+                                VAMPOMI_MEM_HOST) != VAMPOMI_OK)
+        return die("association test (loo, several phenotypes)");
+    for (size_t t = 0; t < T; ++t) {
+        const std::string out = opt.out_dir + "/" + traits[t].name + "_it_" + traits[t].it_str + "_pval_loo.bin";
+        if (rank == 0) std::cout << "Storing p-values to file " + out << std::endl;
+        if (!vio::store_vec(out, pvals.data() + t * (size_t)M, S, M)) {
+            std::cout << "FATAL  : cannot write " << out << std::endl;
+            return EXIT_FAILURE;
+        }
+    }
+    return 0;
+}
+
 // --run-mode test (src/main_meth.cpp:112-205): R2 and squared correlation of
 // A.x_est on the test set for the estimate files of iterations
 // --test-iter-range, one _test.csv row each.
@@ -181,7 +249,52 @@ int main(int argc, char** argv) {
     const bool subset = !keep.empty() || opt.phen_na == "drop";
     const int64_t N_file = test_mode ? opt.N_test : opt.N;
     std::vector<int64_t> rows;
-    if (subset) {
+    // --trait-file: the traits, then the rows that all their phenotype files
+    // keep (vio::phen_rows_common also holds the files to one sequence of
+    // individuals), on every rank before any device call as well.  Y: the kept
+    // rows of every trait's values; the context needs no phenotype of its own
+    std::vector<Trait> traits;
+    std::vector<double> Y;
+    if (!opt.trait_file.empty()) {
+        std::string err;
+        if (!read_traits(opt.trait_file, traits, &err)) {
+            std::cout << "FATAL  : " << err << std::endl;
+            return EXIT_FAILURE;
+        }
+        std::vector<std::string> paths;
+        for (const Trait& t : traits) paths.push_back(t.phen);
+        std::vector<int64_t> nas;
+        std::vector<std::vector<double>> values;  // every file is parsed once, here
+        int64_t nf = 0, out = 0;
+        if (vio::phen_rows_common(paths, keep, opt.phen_na == "drop", rows, &nf, &out, &nas, &values, &err) != 0) {
+            std::cout << "FATAL  : sample subset: " << err << std::endl;
+            return EXIT_FAILURE;
+        }
+        if (nf != N_file) {
+            std::cout << "FATAL  : sample subset: the phenotype files have " << nf << " rows, --N is " << N_file
+                      << std::endl;
+            return EXIT_FAILURE;
+        }
+        if (rows.size() < 2) {
+            std::cout << "FATAL  : sample subset: " << rows.size() << " of " << N_file
+                      << " samples are kept (at least 2 are needed)" << std::endl;
+            return EXIT_FAILURE;
+        }
+        for (const std::vector<double>& v : values)  // the kept rows of every trait's values, T columns of n
+            for (const int64_t r : rows) Y.push_back(v[(size_t)r]);
+        if (subset && rank == 0) {
+            std::cout << "INFO   : kept " << rows.size() << " of " << N_file << " samples (" << out
+                      << " not in the keep file, " << N_file - out - (int64_t)rows.size() << " with an NA phenotype)"
+                      << std::endl;
+            bool any = false;
+            for (const int64_t v : nas) any = any || v != 0;
+            if (any) {
+                std::cout << "INFO   : NA phenotypes:";
+                for (size_t t = 0; t < traits.size(); ++t) std::cout << " " << traits[t].name << " " << nas[t];
+                std::cout << std::endl;
+            }
+        }
+    } else if (subset) {
         int64_t nf = 0, out = 0, nas = 0;
         std::string err;
         if (vio::phen_rows(test_mode ? opt.phen_file_test : opt.phen_file, keep, opt.phen_na == "drop", rows, &nf, &out,
@@ -302,7 +415,7 @@ int main(int argc, char** argv) {
     const int standardize = opt.model == "bin_class" ? 0 : 1;
     const std::string& phen = test_mode ? opt.phen_file_test : opt.phen_file;
     const std::string& meth = test_mode ? opt.meth_file_test : opt.meth_file;
-    if (vampomi_read_phen(ctx, phen.c_str(), standardize) != VAMPOMI_OK) return die("phenotype");
+    if (traits.empty() && vampomi_read_phen(ctx, phen.c_str(), standardize) != VAMPOMI_OK) return die("phenotype");
     if (rank == 0) std::cout << "meth file name = " << meth << std::endl;
     if ((opt.meth_dtype == "u16"   ? vampomi_load_meth_file_u16(ctx, meth.c_str())
          : opt.meth_dtype == "f32" ? vampomi_load_meth_file_f32(ctx, meth.c_str())
@@ -338,7 +451,9 @@ int main(int argc, char** argv) {
                   << std::endl;
 
     if (opt.run_mode == "association_test" || test_mode) {
-        const int rc = test_mode ? test_run(ctx, opt, rank, M, S) : association_test(ctx, opt, rank, M, S);
+        const int rc = test_mode          ? test_run(ctx, opt, rank, M, S)
+                       : !traits.empty() ? association_test_traits(ctx, opt, traits, Y, n, standardize, rank, M, S)
+                                         : association_test(ctx, opt, rank, M, S);
         vampomi_barrier(ctx);
         vampomi_close(ctx);
         return rc;

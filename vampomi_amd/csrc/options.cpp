@@ -76,6 +76,7 @@ bool parse(int argc, char** argv, Options& o, std::string& echo) {
         {"--meth-na", {Kind::Str, &o.meth_na, nullptr}},
         {"--meth-na-max-frac", {Kind::Str, nullptr, nullptr}},
         {"--cov-adjust", {Kind::Str, &o.cov_adjust, nullptr}},
+        {"--trait-file", {Kind::Str, &o.trait_file, nullptr}},
     };
     std::stringstream ss;
     ss << "\nardyh command line options:\n";
@@ -197,6 +198,18 @@ bool parse(int argc, char** argv, Options& o, std::string& echo) {
                               : nullptr;
         if (why) {
             std::cout << "FATAL  : option --cov-adjust residual " << why << "!" << std::endl;
+            return false;
+        }
+    }
+    if (!o.trait_file.empty()) {
+        const char* why = o.run_mode != "association_test" ? "needs --run-mode association_test"
+                          : o.pval_method != "loo"         ? "needs --pval-method loo"
+                          : !o.phen_file.empty()           ? "names every phenotype file itself: --phen-file cannot stand beside it"
+                          : !o.estimate_file.empty()       ? "names every estimate file itself: --estimate-file cannot stand beside it"
+                          : !o.r1_file.empty()             ? "cannot be combined with --r1-file"
+                                                           : nullptr;
+        if (why) {
+            std::cout << "FATAL  : option --trait-file " << why << "!" << std::endl;
             return false;
         }
     }

@@ -46,6 +46,11 @@ struct Options {
     // phenotype are replaced at ingest by their residuals on the intercept and
     // the --C columns of --cov-file (--cov-file-test in --run-mode test)
     std::string cov_adjust = "none";
+    // --trait-file F (--run-mode association_test --pval-method loo only):
+    // several phenotypes against one load of the matrix; per non-blank, non-#
+    // line of F: <name> <phen-file> <estimate-file>.  Stands instead of
+    // --phen-file / --estimate-file
+    std::string trait_file;
 };
 
 // Parses argv exactly like Options::read_command_line_options + check_options:
