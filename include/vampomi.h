@@ -48,6 +48,7 @@
 #ifndef VAMPOMI_H
 #define VAMPOMI_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -57,6 +58,7 @@ extern "C" {
 #define VAMPOMI_ABI_VERSION 3
 #define VAMPOMI_MAX_L 64          /* mixture components */
 #define VAMPOMI_MAX_C 64          /* covariates of the probit model */
+#define VAMPOMI_MAX_SEGMENTS 64   /* labels of the leave-one-chromosome-out test */
 #define VAMPOMI_UNIQUE_ID_BYTES 128
 
 typedef enum {
@@ -579,6 +581,44 @@ vampomi_status vampomi_assoc_se(vampomi_ctx* ctx, const double* r1, double gam1,
  * VAMPOMI_ERR_ARG: T < 1, Y NULL, ldY < N; VAMPOMI_ERR_STATE: no matrix loaded. */
 vampomi_status vampomi_assoc_loo_multi(vampomi_ctx* ctx, int T, const double* Y, int64_t ldY, int standardize,
                                        const double* est, double* pvals, double* stats, int mem);
+
+/* COLLECTIVE.  The leave-one-chromosome-out test (--pval-method loco).  Every
+ * local marker j has a label labels[j] in [0, G), 1 <= G <= VAMPOMI_MAX_SEGMENTS
+ * (labels: M values on the host, whatever `mem`).  With x1 = est * sqrt(N) and A
+ * the operator of vampomi_ax,
+ *   z_c = A (x1 restricted to the markers of label c), c = 0 .. G-1: the raw
+ *         partial sums of all G vectors go through ONE all-reduce and are then
+ *         divided by sqrt(N); a label without markers gives zeros;
+ *   z   = z_0 + z_1 + .. + z_{G-1}, added in ascending c;
+ *   y_c = (y - z) + z_c, in that order: y without the fitted effect of every
+ *         marker outside label c;
+ * and marker j is tested marginally against y_c, c = labels[j]: the five sums
+ * sumx sumsqx sumxy sumy sumsqy over the RAW column and y_c, then
+ * vampomi_assoc_loo's p-value (N - 2 degrees of freedom).  A marker's sums are,
+ * bit for bit, those of vampomi_assoc_loo_multi(ctx, 1, y_c, .., standardize 0,
+ * est NULL, ..) on a plain context.  est == NULL (on every rank) stands for all
+ * zeros: every y_c is y exactly and no A.x pass runs.
+ * pvals (M), stats (5*M) in `mem`, each may be NULL; resid (host, G x N, may be
+ * NULL): y_c for every c, the same on every rank.
+ * Two passes over the matrix whatever G is: a segmented A.x over the markers
+ * sorted by (label, index), counted in vampomi_stats.ax (K = 1), and the marker
+ * pass, counted in vampomi_stats.loo; every sum has a fixed order, so the
+ * results are bitwise repeatable.  Workspaces are allocated at the first call.
+ * VAMPOMI_ERR_ARG: labels NULL with M > 0, G outside [1, VAMPOMI_MAX_SEGMENTS],
+ * a label outside [0, G); VAMPOMI_ERR_STATE: no matrix or no phenotype. */
+vampomi_status vampomi_assoc_loco(vampomi_ctx* ctx, const double* est, const int32_t* labels, int G, double* pvals,
+                                  double* stats, double* resid, int mem);
+/* The label file of --loco-file; needs no device.  The file holds exactly Mt
+ * whitespace-separated tokens (blanks, tabs, newlines, blank lines), one per
+ * marker in file order; tokens are free text ("1", "X", "chr7") and are
+ * numbered by first appearance.  labels (Mt entries, may be NULL) receives the
+ * numbers, *G their count, names (may be NULL) the distinct tokens in that
+ * order, each followed by '\n' and the whole by a NUL, if names_cap holds them
+ * (VAMPOMI_ERR_ARG otherwise).  VAMPOMI_ERR_IO: the file cannot be opened;
+ * VAMPOMI_ERR_ARG: a token count other than Mt, or more than
+ * VAMPOMI_MAX_SEGMENTS distinct tokens (vampomi_last_error says which). */
+vampomi_status vampomi_read_labels(const char* path, int64_t Mt, int32_t* labels, int* G, char* names,
+                                   size_t names_cap);
 
 /* ---- --run-mode test (src/main_meth.cpp:112-205) ----
  * On a context holding the TEST data set (N = N_test, its own marker

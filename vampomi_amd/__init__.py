@@ -24,7 +24,7 @@ from ._lib import (CLI_PATH, GEN_GAUSS, GEN_METH, LIB_PATH, MAX_L, MEM_DEVICE, M
                    STORE_F32, STORE_F64, STORE_U16, UNIQUE_ID_BYTES, Params, Result, ShardDesc, Stats, VampomiError,
                    check, load)
 
-__all__ = ["Data", "Vamp", "VampOptions", "divide_work", "comm_unique_id", "phen_rows", "phen_rows_common", "adjust_basis", "VampomiError", "LIB_PATH", "CLI_PATH",
+__all__ = ["Data", "Vamp", "VampOptions", "divide_work", "comm_unique_id", "phen_rows", "phen_rows_common", "read_labels", "adjust_basis", "VampomiError", "LIB_PATH", "CLI_PATH",
            "GEN_GAUSS", "GEN_METH", "STORE_F64", "STORE_F32", "STORE_U16", "load"]
 
 _STORAGE = {"f64": STORE_F64, "f32": STORE_F32, "u16": STORE_U16}
@@ -87,6 +87,28 @@ def phen_rows_common(paths, keep_file: Optional[str] = None, drop_na: bool = Fal
     check(lib.vampomi_phen_rows_common(arr, len(paths), keep, 1 if drop_na else 0, _dp(rows), n.value, C.byref(nf),
                                        C.byref(n), _dp(na)))
     return rows[: n.value], nf.value, na[: len(paths)]
+
+
+def read_labels(path: str, Mt: int):
+    """(labels, names): the --loco-file ``path`` (vampomi_read_labels; no
+    device needed).  The file holds exactly ``Mt`` whitespace-separated tokens,
+    one per marker in file order; ``labels`` (int32, Mt) numbers them by first
+    appearance and ``names`` lists the distinct tokens in that order.  Another
+    token count or more than 64 distinct tokens raises status 1."""
+    lib = load()
+    lab = np.zeros(max(int(Mt), 1), dtype=np.int32)
+    G = C.c_int()
+    cap = 1 << 16
+    while True:
+        buf = C.create_string_buffer(cap)
+        st = lib.vampomi_read_labels(str(path).encode(), int(Mt), _dp(lab), C.byref(G), buf, cap)
+        if st == 1 and b"names_cap" in lib.vampomi_last_error() and cap < (1 << 28):
+            cap *= 16
+            continue
+        check(st)
+        break
+    names = buf.value.decode().split("\n")[: G.value]
+    return lab[: int(Mt)], names
 
 
 def adjust_basis(Z: np.ndarray):
@@ -503,6 +525,37 @@ class Data:
         check(self._lib.vampomi_assoc_loo_multi(self.ctx, T, _dp(Y), self.N, 1 if standardize else 0,
                                                 None if est is None else _dp(est), _dp(pv), _dp(st), MEM_HOST))
         return pv[:, : self.M], st[:, : self.M]
+
+    def assoc_loco(self, est: Optional[np.ndarray], labels: np.ndarray, G: Optional[int] = None,
+                   resid: bool = False):
+        """The leave-one-chromosome-out test (vampomi_assoc_loco).  ``labels``:
+        the M local markers' labels in [0, G) (``G`` None: max + 1 of the local
+        labels, for one rank); marker j is tested marginally against
+        ``y_c = (y - z) + z_c``, c = labels[j], the phenotype without the
+        fitted effect of every marker outside label c.  ``est``: the
+        estimate-file slice (M), or None for all zeros (every y_c is y, no A.x
+        pass).  COLLECTIVE.  Two passes over the matrix whatever G is.
+        Returns (pvals (M), stats (M, 5)) and with ``resid`` also R (G, N),
+        R[c] = y_c."""
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        if labels.shape != (self.M,):
+            raise ValueError("labels must be (M,)")
+        if G is None:
+            G = int(labels.max()) + 1 if labels.size else 1
+        if est is not None:
+            est = np.ascontiguousarray(est, dtype=np.float64)
+            if est.shape != (self.M,):
+                raise ValueError("estimates must be (M,)")
+            if est.size == 0:  # an empty shard still takes part in the all-reduce: a non-null pointer
+                est = np.zeros(1)
+        if labels.size == 0:
+            labels = np.zeros(1, dtype=np.int32)
+        pv = np.zeros(max(self.M, 1))
+        st = np.zeros((max(self.M, 1), 5))
+        R = np.zeros((max(int(G), 1), self.N)) if resid else None
+        check(self._lib.vampomi_assoc_loco(self.ctx, None if est is None else _dp(est), _dp(labels), int(G), _dp(pv),
+                                           _dp(st), None if R is None else _dp(R), MEM_HOST))
+        return (pv[: self.M], st[: self.M], R) if resid else (pv[: self.M], st[: self.M])
 
     def assoc_se(self, r1: np.ndarray, gam1: float) -> np.ndarray:
         """--pval-method se (src/main_meth.cpp:218-242)."""

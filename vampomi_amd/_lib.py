@@ -149,6 +149,8 @@ SIGNATURES = {
     "vampomi_assoc_loo": (C.c_int, [_P, _P, _P, _P, C.c_int]),
     "vampomi_assoc_se": (C.c_int, [_P, _P, C.c_double, _P, C.c_int]),
     "vampomi_assoc_loo_multi": (C.c_int, [_P, C.c_int, _P, C.c_int64, C.c_int, _P, _P, _P, C.c_int]),
+    "vampomi_assoc_loco": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, C.c_int]),
+    "vampomi_read_labels": (C.c_int, [C.c_char_p, C.c_int64, _P, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
     "vampomi_update_prior": (C.c_int, [_P, _P, C.c_double, C.POINTER(C.c_int), _P, _P, C.c_int, C.c_double,
                                         C.c_int, C.c_double, C.c_int]),
     "vampomi_denoise_bin": (C.c_int, [_P, _P, C.c_double, _P, C.POINTER(C.c_double), C.c_int]),

@@ -203,6 +203,15 @@ struct vampomi_ctx {
     // M-vectors (estimates, x1, p-values, then the 5 sums of each phenotype)
     double* am_n = nullptr;
     double* am_m = nullptr;
+    // vampomi_assoc_loco's workspaces (allocated on first use, grown when a
+    // call needs more): lc_z, lc_G ld-vectors (z_c, then y_c in place; pad rows
+    // zero); lc_part, lc_slots partial slots of the segmented A.x (ld each);
+    // lc_idx, the lists of vk::SegLists (lc_idx_cap words)
+    double* lc_z = nullptr;
+    double* lc_part = nullptr;
+    int32_t* lc_idx = nullptr;
+    int lc_G = 0;
+    int64_t lc_slots = 0, lc_idx_cap = 0;
 
     bool timing = false;
     int tperiod = 1;            // time 1 in tperiod launches of each (class, K)

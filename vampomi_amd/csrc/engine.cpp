@@ -1136,8 +1136,13 @@ void release_ctx_resources(vampomi_ctx* c) {
     if (c->na_cnt) (void)hipFree(c->na_cnt);
     c->na_cnt = nullptr;
     for (double** p : {&c->mave, &c->msig, &c->y, &c->ax_part, &c->red_part, &c->scal, &c->nbuf, &c->mbuf,
-                       &c->op_part, &c->op_nvec, &c->cov_Z, &c->cov_part, &c->cov_dev, &c->am_n, &c->am_m})
+                       &c->op_part, &c->op_nvec, &c->cov_Z, &c->cov_part, &c->cov_dev, &c->am_n, &c->am_m, &c->lc_z,
+                       &c->lc_part})
         dev_free(*p);
+    if (c->lc_idx) (void)hipFree(c->lc_idx);
+    c->lc_idx = nullptr;
+    c->lc_G = 0;
+    c->lc_slots = c->lc_idx_cap = 0;
     if (c->op_xg) (void)hipFree(c->op_xg);
     c->op_xg = nullptr;
     if (c->op_ts) (void)hipFree(c->op_ts);
@@ -2499,6 +2504,133 @@ extern "C" vampomi_status vampomi_assoc_loo_multi(vampomi_ctx* c, int T, const d
     }
     STCHK(sync_stream(c, c->st));
     if (c->timing) resolve_timing(c);
+    return VAMPOMI_OK;
+}
+
+// The leave-one-chromosome-out test: the segmented A.x over
+// the markers sorted by (label, index), z and y_c, the marker pass against the
+// phenotype of each marker's label.  COLLECTIVE (one all-reduce of G ld-vectors;
+// none with est == NULL, which is NULL on every rank or on none).
+extern "C" vampomi_status vampomi_assoc_loco(vampomi_ctx* c, const double* est, const int32_t* labels, int G,
+                                             double* pvals, double* stats, double* resid, int mem) {
+    CollScope cs_(c);
+    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
+    if (!labels && c->M > 0) return fail(VAMPOMI_ERR_ARG, "assoc_loco: null labels");
+    if (G < 1 || G > vk::kSegMax)
+        return fail(VAMPOMI_ERR_ARG, "assoc_loco: G = " + std::to_string(G) + " outside [1, " +
+                                         std::to_string(vk::kSegMax) + "]");
+    for (int64_t i = 0; i < c->M; ++i)
+        if (labels[i] < 0 || labels[i] >= G)
+            return fail(VAMPOMI_ERR_ARG, "assoc_loco: label " + std::to_string(labels[i]) + " of marker " +
+                                             std::to_string(i) + " outside [0, " + std::to_string(G) + ")");
+    if (!c->have_X || !c->have_y) return fail(VAMPOMI_ERR_STATE, "load methylation data and phenotype first");
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t M = c->M, N = c->N, Mx = std::max<int64_t>(M, 1), ld = c->ld;
+    vk::SegLists L;
+    vk::seg_lists(labels, M, G, &L);
+    const int nchunks = L.nchunks(), ngroups = L.ngroups();
+    // the lists in one device block: cols, chunk_at, lab_chunk, grp_col, grp_lab
+    const int64_t o_chunk = M, o_lab = o_chunk + nchunks + 1, o_gcol = o_lab + G + 1,
+                  o_glab = o_gcol + (int64_t)ngroups * vk::kLocoG, words = o_glab + ngroups;
+    if (words > c->lc_idx_cap) {
+        if (c->lc_idx) (void)hipFree(c->lc_idx);
+        c->lc_idx = nullptr;
+        c->lc_idx_cap = 0;
+        // (what any labelling of this shard needs, so a later call does not grow it)
+        const int64_t cap = M + vk::seg_max_chunks(M) + 1 + vk::kSegMax + 1 + vk::seg_max_groups(M) * (vk::kLocoG + 1);
+        hipError_t e = hipMalloc((void**)&c->lc_idx, (size_t)cap * sizeof(int32_t));
+        if (e != hipSuccess) return fail(VAMPOMI_ERR_OOM, std::string("hipMalloc(label lists): ") + hipGetErrorString(e));
+        c->lc_idx_cap = cap;
+    }
+    std::vector<int32_t> host((size_t)words);
+    std::copy(L.cols.begin(), L.cols.end(), host.begin());
+    std::copy(L.chunk_at.begin(), L.chunk_at.end(), host.begin() + o_chunk);
+    std::copy(L.lab_chunk.begin(), L.lab_chunk.end(), host.begin() + o_lab);
+    std::copy(L.grp_col.begin(), L.grp_col.end(), host.begin() + o_gcol);
+    std::copy(L.grp_lab.begin(), L.grp_lab.end(), host.begin() + o_glab);
+    HIPCHK(hipMemcpyAsync(c->lc_idx, host.data(), (size_t)words * sizeof(int32_t), hipMemcpyHostToDevice, c->st));
+    STCHK(sync_stream(c, c->st));  // host is a local: the copy has left it
+    double* pv = c->mbuf + 2 * Mx;  // p-values
+    double* st = c->mbuf + 3 * Mx;  // 5 sums per marker
+    const double* ys = c->y;        // est == NULL: every y_c is y
+    int64_t ldy = 0;
+    if (est) {
+        if (G > c->lc_G) {
+            dev_free(c->lc_z);
+            c->lc_G = 0;
+            STCHK(dev_alloc(&c->lc_z, (size_t)G * ld));
+            HIPCHK(hipMemsetAsync(c->lc_z, 0, (size_t)G * ld * 8, c->st));  // pad rows stay zero
+            c->lc_G = G;
+        }
+        if (nchunks > c->lc_slots) {
+            dev_free(c->lc_part);
+            c->lc_slots = 0;
+            STCHK(dev_alloc(&c->lc_part, (size_t)nchunks * ld));
+            c->lc_slots = nchunks;
+        }
+        double* e = c->mbuf;        // estimate-file values
+        double* x1 = c->mbuf + Mx;  // x1_hat * sqrt(N)
+        STCHK(stage_in(c, est, M, mem, e));
+        HIPCHK(vk::mul_scalar(M, e, std::sqrt((double)N), x1, c->st));
+        // X once, the lists and x1, one slot per chunk written and read back
+        TimedLaunch t = launch_stat(c, 0, 1, pass_bytes(c, 1) + 16.0 * (double)N * nchunks, pass_flops(c, 1));
+        HIPCHK(vk::ax_seg_partial(c->shard(), x1, c->lc_idx, c->lc_idx + o_chunk, nchunks, c->lc_part, c->st,
+                                  vk::Timing{t.a, t.b}));
+        c->stats.a_passes_exec++;
+        if (!c->use_comm) {
+            HIPCHK(vk::ax_seg_reduce(G, N, ld, c->lc_idx + o_lab, c->lc_part, c->lc_z, c->sqrtN, c->st));
+            HIPCHK(vk::loco_resid(G, N, ld, c->y, c->lc_z, 0.0, c->st));
+        } else {
+            HIPCHK(vk::ax_seg_reduce(G, N, ld, c->lc_idx + o_lab, c->lc_part, c->lc_z, 0.0, c->st));
+            STCHK(allreduce_dev(c, c->lc_z, (size_t)G * ld));  // ONE all-reduce for all G vectors
+            HIPCHK(vk::loco_resid(G, N, ld, c->y, c->lc_z, c->sqrtN, c->st));
+        }
+        ys = c->lc_z;
+        ldy = ld;
+    }
+    // raw X once, G phenotypes, the lists, five sums per marker; per element 5
+    // accumulations (3 of them products) less the two shared ones of a group
+    TimedLaunch t = launch_stat(c, 2, 1,
+                                (double)c->esize() * (double)N * (double)M + 8.0 * (double)N * (est ? G : 1) +
+                                    8.0 * 6.0 * (double)M,
+                                7.0 * (double)N * (double)M);
+    HIPCHK(vk::loco_sums(c->shard(), ys, ldy, c->lc_idx + o_gcol, c->lc_idx + o_glab, ngroups, st, c->st,
+                         vk::Timing{t.a, t.b}));
+    c->stats.a_passes_exec++;
+    HIPCHK(vk::loo_pvals(M, st, (int)N, pv, c->st));
+    if (resid)
+        for (int g = 0; g < G; ++g)
+            HIPCHK(hipMemcpyAsync(resid + (int64_t)g * N, ys + (int64_t)g * ldy, (size_t)N * 8, hipMemcpyDeviceToHost,
+                                  c->st));
+    if (stats) STCHK(stage_out(c, st, 5 * M, mem, stats));
+    if (pvals) STCHK(stage_out(c, pv, M, mem, pvals));
+    STCHK(sync_stream(c, c->st));
+    if (c->timing) resolve_timing(c);
+    return VAMPOMI_OK;
+}
+
+extern "C" vampomi_status vampomi_read_labels(const char* path, int64_t Mt, int32_t* labels, int* G, char* names,
+                                              size_t names_cap) {
+    if (!path || Mt < 0) return fail(VAMPOMI_ERR_ARG, "read_labels: null path or Mt < 0");
+    std::vector<int32_t> lab;
+    std::vector<std::string> nm;
+    std::vector<int64_t> cnt;
+    std::string err;
+    switch (vio::read_labels(path, Mt, vk::kSegMax, lab, nm, cnt, &err)) {
+        case 0: break;
+        case -1: return fail(VAMPOMI_ERR_IO, err);
+        default: return fail(VAMPOMI_ERR_ARG, err);
+    }
+    if (labels) std::copy(lab.begin(), lab.end(), labels);
+    if (G) *G = (int)nm.size();
+    if (names) {
+        std::string all;
+        for (const std::string& s : nm) all += s + "\n";
+        if (all.size() + 1 > names_cap)
+            return fail(VAMPOMI_ERR_ARG, "read_labels: names_cap holds " + std::to_string(names_cap) + " bytes, " +
+                                             std::to_string(all.size() + 1) + " are needed");
+        std::memcpy(names, all.c_str(), all.size() + 1);
+    }
     return VAMPOMI_OK;
 }
 

@@ -226,6 +226,46 @@ void standardize_covariates(double* Z, int64_t N, int C, int64_t ld) {
     }
 }
 
+int read_labels(const std::string& path, int64_t Mt, int max_labels, std::vector<int32_t>& labels,
+                std::vector<std::string>& names, std::vector<int64_t>& counts, std::string* err) {
+    std::ifstream in(path);
+    if (!in) {
+        if (err) *err = "cannot open label file " + path;
+        return -1;
+    }
+    labels.clear();
+    names.clear();
+    counts.clear();
+    std::map<std::string, int32_t> seen;
+    std::string tok;
+    int64_t n = 0;
+    while (in >> tok) {  // operator>> splits on any run of whitespace
+        ++n;
+        if (n > Mt) continue;  // (counted on, for the message)
+        auto it = seen.find(tok);
+        if (it == seen.end()) {
+            if ((int)names.size() == max_labels) {
+                if (err)
+                    *err = "label file " + path + " has more than " + std::to_string(max_labels) +
+                           " distinct labels (the next is '" + tok + "' at marker " + std::to_string(n - 1) + ")";
+                return -3;
+            }
+            it = seen.emplace(tok, (int32_t)names.size()).first;
+            names.push_back(tok);
+            counts.push_back(0);
+        }
+        labels.push_back(it->second);
+        counts[it->second]++;
+    }
+    if (n != Mt) {
+        if (err)
+            *err = "label file " + path + " has " + std::to_string(n) + " labels, expected " + std::to_string(Mt) +
+                   " (one per marker)";
+        return -2;
+    }
+    return 0;
+}
+
 int read_covariates(const std::string& path, int64_t N, int C, bool standardize, double* out, std::string* err) {
     if (C == 0) return 0;  // :161-162
     std::ifstream in(path);

@@ -43,6 +43,15 @@ int phen_rows_common(const std::vector<std::string>& phen_paths, const std::stri
                      std::vector<int64_t>& rows, int64_t* N_file, int64_t* not_kept,
                      std::vector<int64_t>* na_per_file, std::vector<std::vector<double>>* values, std::string* err);
 
+// The label file of the leave-one-chromosome-out test (--loco-file): exactly Mt
+// whitespace-separated tokens (any mix of blanks, tabs, newlines, blank lines),
+// one per marker in file order, free text; labels[i] numbers marker i's token
+// by first appearance, names[c] is token c and counts[c] its markers.  0 ok;
+// -1 cannot open; -2 a token count other than Mt; -3 more than max_labels
+// distinct tokens (*err says what was found).
+int read_labels(const std::string& path, int64_t Mt, int max_labels, std::vector<int32_t>& labels,
+                std::vector<std::string>& names, std::vector<int64_t>& counts, std::string* err);
+
 // data::read_covariates (src/data.cpp:159-227): a header line, then per row
 // two IDs and exactly C numeric fields, split like read_phen's.  out: C
 // columns of N (covariate-major).  0 ok; -1 cannot open; -2 a row without

@@ -6,6 +6,7 @@
 #include <atomic>
 #include <cstdint>
 #include <string>
+#include <vector>
 
 namespace vk {
 
@@ -616,6 +617,49 @@ hipError_t loo_multi_sums(const Shard& s, int KT, const double* ymod, const doub
                           hipStream_t st, const Timing& tm = Timing{});
 std::string loo_multi_kernel_name(int KT, int ek = 0);
 std::string loo_kernel_name(int variant, int ek = 0);
+// ---- leave-one-chromosome-out test --------------------------
+// Each marker has a label in [0, G), G <= kSegMax.  Both passes walk the local
+// markers sorted by (label, index), through lists the host cuts (seg_lists):
+//   cols       the M sorted column indices
+//   chunk_at   nchunks + 1 offsets into cols: chunk k is [chunk_at[k],
+//              chunk_at[k + 1]), at most kSegChunk columns of ONE label; a
+//              label's run of n columns is cut into ceil(n / kSegChunk) equal
+//              shares
+//   lab_chunk  G + 1: label c's chunks are [lab_chunk[c], lab_chunk[c + 1])
+//   grp_col    ngroups x kLocoG columns of ONE label (-1: none), grp_lab its label
+constexpr int kSegMax = 64;      // VAMPOMI_MAX_SEGMENTS
+constexpr int kSegChunk = 256;   // columns per chunk at most
+constexpr int kSegRows = 512;    // rows per tile of the segmented A.x
+constexpr int kLocoG = 4;        // markers per workgroup of the marker pass (kLooDefault's)
+struct SegLists {
+    std::vector<int32_t> cols, chunk_at, lab_chunk, grp_col, grp_lab;
+    int nchunks() const { return (int)chunk_at.size() - 1; }
+    int ngroups() const { return (int)grp_lab.size(); }
+};
+inline int64_t seg_max_chunks(int64_t M) { return (M + kSegChunk - 1) / kSegChunk + kSegMax; }
+inline int64_t seg_max_groups(int64_t M) { return (M + kLocoG - 1) / kLocoG + kSegMax; }
+// labels: M values in [0, G) (checked by the caller)
+void seg_lists(const int32_t* labels, int64_t M, int G, SegLists* out);
+// Stage 1: workgroup (chunk, row tile of kSegRows) adds the terms (X_ij -
+// mave_i) * (msig_i * x_i), formed as ax_partial forms them, over the chunk's
+// columns in list order into part[chunk][j] (nchunks x ld; rows j < N).
+// Stage 2 (ax_seg_reduce): z[c][j] = label c's slots added in chunk order
+// (zeros for a label without markers), / div if div > 0; z: G x ld, pad rows
+// not written.  Every sum has a fixed order: no atomics.
+hipError_t ax_seg_partial(const Shard& s, const double* x, const int32_t* cols, const int32_t* chunk_at, int nchunks,
+                          double* part, hipStream_t st, const Timing& tm = Timing{});
+hipError_t ax_seg_reduce(int G, int64_t N, int64_t ld, const int32_t* lab_chunk, const double* part, double* z,
+                         double div, hipStream_t st);
+// zc[c][j] = (y[j] - z) + z_c[j] in place, z = z_0 + ... + z_{G-1} in ascending
+// c and z_c = zc[c][j] (/ div if div > 0: the all-reduced raw sums)
+hipError_t loco_resid(int G, int64_t N, int64_t ld, const double* y, double* zc, double div, hipStream_t st);
+// stats[5j + {0..4}] for every marker j of the groups: the five sums of
+// loo_sums(s, ys + lab[j] * ldy, x1 = 0) under any 8-wave workgroup variant
+// (kLooDefault among them), bit for bit.  ldy = 0: one phenotype for all
+hipError_t loco_sums(const Shard& s, const double* ys, int64_t ldy, const int32_t* grp_col, const int32_t* grp_lab,
+                     int ngroups, double* stats, hipStream_t st, const Timing& tm = Timing{});
+std::string ax_seg_kernel_name(int ek = 0);
+std::string loco_kernel_name(int ek = 0);
 int loo_variant_count();
 bool loo_variant_ok(int v);
 // pvals[j] = linear_reg1d_pvals(stats[5j..5j+4], n)  (src/utilities.cpp:269-282)

@@ -3932,6 +3932,351 @@ hipError_t loo_multi_sums(const Shard& s, int KT, const double* ymod, const doub
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// leave-one-chromosome-out test
+// ---------------------------------------------------------------------------
+// The lists both passes walk.  A label's markers are not contiguous in an
+// array-ordered file, so the local markers are sorted by (label, index) and
+// the sorted list is cut twice, never across a label: into chunks of at most
+// kSegChunk columns (equal shares of a label's run) for the segmented A.x,
+// and into groups of kLocoG columns (a label's last group padded with -1) for
+// the marker pass.
+void seg_lists(const int32_t* labels, int64_t M, int G, SegLists* out) {
+    SegLists& L = *out;
+    std::vector<int32_t> count(G + 1, 0);
+    for (int64_t i = 0; i < M; ++i) count[labels[i] + 1]++;
+    for (int c = 0; c < G; ++c) count[c + 1] += count[c];  // label c's run is [count[c], count[c + 1])
+    L.cols.assign((size_t)M, 0);
+    {
+        std::vector<int32_t> at(count.begin(), count.end() - 1);
+        for (int64_t i = 0; i < M; ++i) L.cols[at[labels[i]]++] = (int32_t)i;  // stable: ascending index inside a label
+    }
+    L.chunk_at.clear();
+    L.lab_chunk.assign(1, 0);
+    L.grp_col.clear();
+    L.grp_lab.clear();
+    for (int c = 0; c < G; ++c) {
+        const int64_t b = count[c], n = count[c + 1] - b;
+        const int64_t nch = cdiv(n, kSegChunk);
+        for (int64_t k = 0; k < nch; ++k) L.chunk_at.push_back((int32_t)(b + k * n / nch));
+        L.lab_chunk.push_back((int32_t)L.chunk_at.size());
+        for (int64_t i = 0; i < n; i += kLocoG) {
+            for (int g = 0; g < kLocoG; ++g) L.grp_col.push_back(i + g < n ? L.cols[b + i + g] : -1);
+            L.grp_lab.push_back(c);
+        }
+    }
+    L.chunk_at.push_back((int32_t)M);
+}
+
+// Segmented A.x, stage 1: workgroup (chunk ch, row tile t) streams the
+// kSegRows rows of tile t of the chunk's columns, in list order, and stores
+// partial slot ch.  Rows per lane as ax_partial's R = 2 tiles (wave w the slab
+// of 128 rows, lane l rows 2l and 2l + 1: one row pair per column), U columns
+// loaded before any arithmetic, the term (x - mave_i) * (msig_i * x_i) as
+// ax_piece forms it.  The tile is the fast index of the grid, so workgroups
+// resident together read neighbouring pieces of the same columns.
+template <int U, class XE>
+__device__ __forceinline__ void ax_seg_body(const XE* __restrict__ X, int64_t ld, int64_t N,
+                                            const double* __restrict__ mave, const double* __restrict__ msig,
+                                            const double* __restrict__ x, const int32_t* __restrict__ cols,
+                                            const int32_t* __restrict__ chunk_at, int64_t tiles,
+                                            double* __restrict__ part) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t ch = (int64_t)blockIdx.x / tiles, t = (int64_t)blockIdx.x - ch * tiles;
+    const int64_t j0 = t * kSegRows + (int64_t)wave * 128 + 2 * lane;
+    if (j0 >= N) return;  // (no barrier below)
+    const int i1 = chunk_at[ch + 1];
+    int i = chunk_at[ch];
+    const XE* base = X + j0;
+    double a0 = 0.0, a1 = 0.0;
+    for (; i + (U - 1) < i1; i += U) {
+        int64_t c[U];
+        xpair_t<XE> xv[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            c[u] = cols[i + u];
+            xv[u] = ldx<true>(base + c[u] * ld);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const double ave = mave[c[u]];
+            const double w = msig[c[u]] * x[c[u]];
+            a0 += (widen(xv[u]).x - ave) * w;
+            a1 += (widen(xv[u]).y - ave) * w;
+        }
+    }
+    for (; i < i1; ++i) {
+        const int64_t c = cols[i];
+        const v2d xv = widen(ldx<true>(base + c * ld));
+        const double ave = mave[c];
+        const double w = msig[c] * x[c];
+        a0 += (xv.x - ave) * w;
+        a1 += (xv.y - ave) * w;
+    }
+    double* dst = part + ch * ld + j0;
+    dst[0] = a0;
+    if (j0 + 1 < N) dst[1] = a1;
+}
+
+template <int U>
+__global__ __launch_bounds__(kBlock) void ax_seg_kernel(const double* __restrict__ X, int64_t ld, int64_t N,
+                                                        const double* __restrict__ mave,
+                                                        const double* __restrict__ msig, const double* __restrict__ x,
+                                                        const int32_t* __restrict__ cols,
+                                                        const int32_t* __restrict__ chunk_at, int64_t tiles,
+                                                        double* __restrict__ part) {
+    ax_seg_body<U>(X, ld, N, mave, msig, x, cols, chunk_at, tiles, part);
+}
+
+template <int U>
+__global__ __launch_bounds__(kBlock) void ax_seg_kernel_f32(const float* __restrict__ X, int64_t ld, int64_t N,
+                                                            const double* __restrict__ mave,
+                                                            const double* __restrict__ msig,
+                                                            const double* __restrict__ x,
+                                                            const int32_t* __restrict__ cols,
+                                                            const int32_t* __restrict__ chunk_at, int64_t tiles,
+                                                            double* __restrict__ part) {
+    ax_seg_body<U>(X, ld, N, mave, msig, x, cols, chunk_at, tiles, part);
+}
+
+template <int U>
+__global__ __launch_bounds__(kBlock) void ax_seg_kernel_u16(const uint16_t* __restrict__ X, int64_t ld, int64_t N,
+                                                            const double* __restrict__ mave,
+                                                            const double* __restrict__ msig,
+                                                            const double* __restrict__ x,
+                                                            const int32_t* __restrict__ cols,
+                                                            const int32_t* __restrict__ chunk_at, int64_t tiles,
+                                                            double* __restrict__ part) {
+    ax_seg_body<U>(X, ld, N, mave, msig, x, cols, chunk_at, tiles, part);
+}
+
+constexpr int kSegU = 8;  // columns in flight (ax_partial's default variant)
+
+std::string ax_seg_kernel_name(int ek) {
+    char b[48];
+    std::snprintf(b, sizeof b, "ax_seg_kernel%s<%d>", xe_suffix(ek), kSegU);
+    return b;
+}
+
+hipError_t ax_seg_partial(const Shard& s, const double* x, const int32_t* cols, const int32_t* chunk_at, int nchunks,
+                          double* part, hipStream_t st, const Timing& tm) {
+    if (nchunks <= 0 || s.N <= 0) return hipSuccess;
+    const int64_t tiles = cdiv(s.N, kSegRows);
+    if (tiles * nchunks > 0x7fffffffLL) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(tiles * nchunks)), block(kBlock);
+    if (s.u16)
+        hipExtLaunchKernelGGL((ax_seg_kernel_u16<kSegU>), grid, block, 0, st, tm.start, tm.stop, 0, s.x16(), s.ld, s.N,
+                              s.mave, s.msig, x, cols, chunk_at, tiles, part);
+    else if (s.f32)
+        hipExtLaunchKernelGGL((ax_seg_kernel_f32<kSegU>), grid, block, 0, st, tm.start, tm.stop, 0, s.x32(), s.ld, s.N,
+                              s.mave, s.msig, x, cols, chunk_at, tiles, part);
+    else
+        hipExtLaunchKernelGGL((ax_seg_kernel<kSegU>), grid, block, 0, st, tm.start, tm.stop, 0, s.x64(), s.ld, s.N,
+                              s.mave, s.msig, x, cols, chunk_at, tiles, part);
+    return hipGetLastError();
+}
+
+// Stage 2: z[c][j] = the slots of label c's chunks added in chunk order
+// (zero for a label without chunks); if div > 0 then / div.  Pad rows are not
+// written.  grid: (N / kBlock, G)
+__global__ __launch_bounds__(kBlock) void ax_seg_reduce_kernel(int64_t N, int64_t ld,
+                                                               const int32_t* __restrict__ lab_chunk,
+                                                               const double* __restrict__ part,
+                                                               double* __restrict__ z, double div) {
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= N) return;
+    const int c = blockIdx.y;
+    const int k1 = lab_chunk[c + 1];
+    int k = lab_chunk[c];
+    const double* p = part + j;
+    double s = 0.0;
+    for (; k + 4 <= k1; k += 4) {
+        const double q0 = p[(int64_t)(k + 0) * ld], q1 = p[(int64_t)(k + 1) * ld];
+        const double q2 = p[(int64_t)(k + 2) * ld], q3 = p[(int64_t)(k + 3) * ld];
+        s += q0;
+        s += q1;
+        s += q2;
+        s += q3;
+    }
+    for (; k < k1; ++k) s += p[(int64_t)k * ld];
+    if (div > 0.0) s /= div;
+    z[(int64_t)c * ld + j] = s;
+}
+
+hipError_t ax_seg_reduce(int G, int64_t N, int64_t ld, const int32_t* lab_chunk, const double* part, double* z,
+                         double div, hipStream_t st) {
+    if (G <= 0 || N <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ax_seg_reduce_kernel, dim3((unsigned)cdiv(N, kBlock), (unsigned)G), dim3(kBlock), 0, st, N, ld,
+                       lab_chunk, part, z, div);
+    return hipGetLastError();
+}
+
+// z = z_0 + z_1 + ... + z_{G-1} (ascending c), then zc[c][j] = (y[j] - z) +
+// z_c[j] in place: y with the fitted effect of every marker outside label c
+// taken out.  div > 0: z_c stands for zc[c] / div (the all-reduced raw sums)
+__global__ __launch_bounds__(kBlock) void loco_resid_kernel(int G, int64_t N, int64_t ld,
+                                                            const double* __restrict__ y, double* zc, double div) {
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= N) return;
+    auto zof = [&](int c) {
+        const double v = zc[(int64_t)c * ld + j];
+        return div > 0.0 ? v / div : v;
+    };
+    double z = zof(0);
+    for (int c = 1; c < G; ++c) z += zof(c);
+    const double ym = y[j] - z;
+    for (int c = 0; c < G; ++c) zc[(int64_t)c * ld + j] = ym + zof(c);
+}
+
+hipError_t loco_resid(int G, int64_t N, int64_t ld, const double* y, double* zc, double div, hipStream_t st) {
+    if (G <= 0 || N <= 0) return hipSuccess;
+    hipLaunchKernelGGL(loco_resid_kernel, dim3((unsigned)cdiv(N, kBlock)), dim3(kBlock), 0, st, G, N, ld, y, zc, div);
+    return hipGetLastError();
+}
+
+// The marker pass: loo_wg_body<kLocoG, UJ, 8> over a group of the list instead
+// of G neighbouring columns, with x1 = 0 and the phenotype of the group's
+// label.  ym = y + q * 0 is y, so the quotient is not formed; rows, per-lane
+// order, wave_sum and the wave-order LDS sum are loo_wg_body's, so a marker's
+// five sums are bit for bit those of loo_wg_kernel<*, *, 8> on (y_c, 0).  The
+// markers of a group share y, and with it sum y and sum y^2 operation for
+// operation: those two are accumulated once per group (acc[3 G], acc[3 G + 1])
+// and stored for each of its markers.
+template <int G, int UJ, int W, class XE>
+__device__ __forceinline__ void loco_body(const XE* __restrict__ X, int64_t ld, int64_t N,
+                                          const double* __restrict__ ys, int64_t ldy,
+                                          const int32_t* __restrict__ grp_col, const int32_t* __restrict__ grp_lab,
+                                          double* __restrict__ stats) {
+    constexpr int NA = 3 * G + 2;
+    __shared__ double part[W][NA];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int32_t* gc = grp_col + (int64_t)blockIdx.x * G;
+    const double* __restrict__ y = ys + (int64_t)grp_lab[blockIdx.x] * ldy;
+    double acc[NA];
+    const XE* col[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const int32_t m = gc[g] >= 0 ? gc[g] : gc[0];  // a pad entry reads the group's first column: discarded
+        col[g] = X + (int64_t)m * ld;
+    }
+#pragma unroll
+    for (int q = 0; q < NA; ++q) acc[q] = 0.0;
+    auto addx = [&](int g, double m, double ym) {
+        acc[3 * g] += m;
+        acc[3 * g + 1] += m * m;
+        acc[3 * g + 2] += m * ym;
+    };
+    auto addy = [&](double ym) {
+        acc[3 * G] += ym;
+        acc[3 * G + 1] += ym * ym;
+    };
+    constexpr int64_t RS = 128 * W;  // rows per load round of the workgroup
+    int64_t j = 2 * lane + 128 * wave;
+    for (; j + RS * (UJ - 1) < N; j += RS * UJ) {
+        v2d yy[UJ];
+        xpair_t<XE> xx[UJ][G];
+#pragma unroll
+        for (int t = 0; t < UJ; ++t)
+#pragma unroll
+            for (int g = 0; g < G; ++g) xx[t][g] = ldx<true>(col[g] + j + RS * t);
+#pragma unroll
+        for (int t = 0; t < UJ; ++t) yy[t] = ld2(y + j + RS * t);
+#pragma unroll
+        for (int t = 0; t < UJ; ++t) {
+            addy(yy[t].x);
+            addy(yy[t].y);
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+            for (int t = 0; t < UJ; ++t) {
+                addx(g, widen(xx[t][g]).x, yy[t].x);
+                addx(g, widen(xx[t][g]).y, yy[t].y);
+            }
+    }
+    for (; j < N; j += RS) {  // (N even or the pad row: ld-padded columns, zero pads)
+        xpair_t<XE> xx[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) xx[g] = ldx<true>(col[g] + j);
+        const v2d yy = ld2(y + j);
+        addy(yy.x);
+        addy(yy.y);
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            addx(g, widen(xx[g]).x, yy.x);
+            addx(g, widen(xx[g]).y, yy.y);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < NA; ++q) {
+        const double s = wave_sum(acc[q]);
+        if (lane == 0) part[wave][q] = s;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < 5 * G) {
+        const int g = threadIdx.x / 5, q = threadIdx.x % 5;
+        const int32_t m = gc[g];
+        if (m >= 0) {
+            const int src = q < 3 ? 3 * g + q : 3 * G + (q - 3);
+            double s = 0.0;
+#pragma unroll
+            for (int w = 0; w < W; ++w) s += part[w][src];
+            stats[5 * (int64_t)m + q] = s;  // the marker's own index
+        }
+    }
+}
+
+template <int G, int UJ, int W>
+__global__ __launch_bounds__(64 * W) void loco_kernel(const double* __restrict__ X, int64_t ld, int64_t N,
+                                                      const double* __restrict__ ys, int64_t ldy,
+                                                      const int32_t* __restrict__ grp_col,
+                                                      const int32_t* __restrict__ grp_lab,
+                                                      double* __restrict__ stats) {
+    loco_body<G, UJ, W>(X, ld, N, ys, ldy, grp_col, grp_lab, stats);
+}
+
+template <int G, int UJ, int W>
+__global__ __launch_bounds__(64 * W) void loco_kernel_f32(const float* __restrict__ X, int64_t ld, int64_t N,
+                                                          const double* __restrict__ ys, int64_t ldy,
+                                                          const int32_t* __restrict__ grp_col,
+                                                          const int32_t* __restrict__ grp_lab,
+                                                          double* __restrict__ stats) {
+    loco_body<G, UJ, W>(X, ld, N, ys, ldy, grp_col, grp_lab, stats);
+}
+
+template <int G, int UJ, int W>
+__global__ __launch_bounds__(64 * W) void loco_kernel_u16(const uint16_t* __restrict__ X, int64_t ld, int64_t N,
+                                                          const double* __restrict__ ys, int64_t ldy,
+                                                          const int32_t* __restrict__ grp_col,
+                                                          const int32_t* __restrict__ grp_lab,
+                                                          double* __restrict__ stats) {
+    loco_body<G, UJ, W>(X, ld, N, ys, ldy, grp_col, grp_lab, stats);
+}
+
+constexpr int kLocoUJ = 2;  // (kLooDefault's: loo_wg_kernel<4, 2, 8>)
+
+std::string loco_kernel_name(int ek) {
+    char b[48];
+    std::snprintf(b, sizeof b, "loco_kernel%s<%d, %d, 8>", xe_suffix(ek), kLocoG, kLocoUJ);
+    return b;
+}
+
+hipError_t loco_sums(const Shard& s, const double* ys, int64_t ldy, const int32_t* grp_col, const int32_t* grp_lab,
+                     int ngroups, double* stats, hipStream_t st, const Timing& tm) {
+    if (ngroups <= 0) return hipSuccess;
+    const dim3 grid((unsigned)ngroups), block(64 * 8);
+    if (s.u16)
+        hipExtLaunchKernelGGL((loco_kernel_u16<kLocoG, kLocoUJ, 8>), grid, block, 0, st, tm.start, tm.stop, 0, s.x16(),
+                              s.ld, s.N, ys, ldy, grp_col, grp_lab, stats);
+    else if (s.f32)
+        hipExtLaunchKernelGGL((loco_kernel_f32<kLocoG, kLocoUJ, 8>), grid, block, 0, st, tm.start, tm.stop, 0, s.x32(),
+                              s.ld, s.N, ys, ldy, grp_col, grp_lab, stats);
+    else
+        hipExtLaunchKernelGGL((loco_kernel<kLocoG, kLocoUJ, 8>), grid, block, 0, st, tm.start, tm.stop, 0, s.x64(),
+                              s.ld, s.N, ys, ldy, grp_col, grp_lab, stats);
+    return hipGetLastError();
+}
+
 // ln B(a, 1/2) and the Student-t upper tail: the same operations as the
 // oracle's orc_lnbeta_half / ibeta_cf / orc_t_sf (oracle/vamp_oracle.c),
 // standing for Boost's complemented students_t cdf (src/utilities.cpp:278-279)

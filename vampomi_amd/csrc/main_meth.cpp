@@ -74,7 +74,8 @@ static bool iteration_of(const std::string& name, std::string& it_str) {
 }
 
 // --run-mode association_test (src/main_meth.cpp:206-264)
-static int association_test(vampomi_ctx* ctx, const vopt::Options& opt, int rank, int64_t M, int64_t S) {
+static int association_test(vampomi_ctx* ctx, const vopt::Options& opt, int rank, int64_t M, int64_t S,
+                            const std::vector<int32_t>& labels, int G) {
     std::vector<double> in((size_t)std::max<int64_t>(M, 1)), pvals((size_t)std::max<int64_t>(M, 1));
     std::string it_str, out;
     if (opt.pval_method == "se") {
@@ -97,6 +98,18 @@ static int association_test(vampomi_ctx* ctx, const vopt::Options& opt, int rank
         if (vampomi_assoc_loo(ctx, in.data(), pvals.data(), nullptr, VAMPOMI_MEM_HOST) != VAMPOMI_OK)
             return die("association test (loo)");
         out = opt.out_dir + "/" + opt.out_name + "_it_" + it_str + "_pval_loo.bin";
+    } else if (opt.pval_method == "loco") {
+        if (!iteration_of(opt.estimate_file, it_str)) {
+            std::cout << "FATAL  : cannot parse the iteration from --estimate-file \"" << opt.estimate_file << "\""
+                      << std::endl;
+            return EXIT_FAILURE;
+        }
+        vio::read_vec(opt.estimate_file, in.data(), S, M);
+        // (labels holds all Mt: this rank's slice is [S, S + M))
+        if (vampomi_assoc_loco(ctx, in.data(), labels.data() + S, G, pvals.data(), nullptr, nullptr,
+                               VAMPOMI_MEM_HOST) != VAMPOMI_OK)
+            return die("association test (loco)");
+        out = opt.out_dir + "/" + opt.out_name + "_it_" + it_str + "_pval_loco.bin";
     } else {
         return 0;  // the reference computes nothing for another --pval-method
     }
@@ -318,6 +331,27 @@ int main(int argc, char** argv) {
     }
     const int64_t n = subset ? (int64_t)rows.size() : N_file;
 
+    // --pval-method loco: the label file, all of it on every rank, before any
+    // device call, so that a bad file ends the job here on all of them
+    std::vector<int32_t> labels;
+    int G = 0;
+    if (!opt.loco_file.empty()) {
+        std::vector<std::string> names;
+        std::vector<int64_t> counts;
+        std::string err;
+        if (vio::read_labels(opt.loco_file, (int64_t)opt.Mt, VAMPOMI_MAX_SEGMENTS, labels, names, counts, &err) != 0) {
+            std::cout << "FATAL  : --loco-file: " << err << std::endl;
+            return EXIT_FAILURE;
+        }
+        G = (int)names.size();
+        if (labels.empty()) labels.push_back(0);  // (never read: a non-null pointer)
+        if (rank == 0) {
+            std::cout << "INFO   : LOCO: " << G << " segments (";
+            for (int c = 0; c < G; ++c) std::cout << (c ? " " : "") << names[(size_t)c] << ":" << counts[(size_t)c];
+            std::cout << ")" << std::endl;
+        }
+    }
+
     // data::read_covariates (src/data.cpp:159-227), on every rank, before any
     // device call: a malformed table ends the job here as it ends the
     // reference's (every rank reads the same file and fails alike).  Only the
@@ -453,7 +487,7 @@ int main(int argc, char** argv) {
     if (opt.run_mode == "association_test" || test_mode) {
         const int rc = test_mode          ? test_run(ctx, opt, rank, M, S)
                        : !traits.empty() ? association_test_traits(ctx, opt, traits, Y, n, standardize, rank, M, S)
-                                         : association_test(ctx, opt, rank, M, S);
+                                         : association_test(ctx, opt, rank, M, S, labels, G);
         vampomi_barrier(ctx);
         vampomi_close(ctx);
         return rc;

@@ -77,6 +77,7 @@ bool parse(int argc, char** argv, Options& o, std::string& echo) {
         {"--meth-na-max-frac", {Kind::Str, nullptr, nullptr}},
         {"--cov-adjust", {Kind::Str, &o.cov_adjust, nullptr}},
         {"--trait-file", {Kind::Str, &o.trait_file, nullptr}},
+        {"--loco-file", {Kind::Str, &o.loco_file, nullptr}},
     };
     std::stringstream ss;
     ss << "\nardyh command line options:\n";
@@ -200,6 +201,19 @@ bool parse(int argc, char** argv, Options& o, std::string& echo) {
             std::cout << "FATAL  : option --cov-adjust residual " << why << "!" << std::endl;
             return false;
         }
+    }
+    if (!o.loco_file.empty()) {
+        const char* why = o.run_mode != "association_test" ? "needs --run-mode association_test"
+                          : o.pval_method != "loco"        ? "needs --pval-method loco"
+                          : !o.trait_file.empty()          ? "cannot be combined with --trait-file"
+                                                           : nullptr;
+        if (why) {
+            std::cout << "FATAL  : option --loco-file " << why << "!" << std::endl;
+            return false;
+        }
+    } else if (o.run_mode == "association_test" && o.pval_method == "loco") {
+        std::cout << "FATAL  : option --pval-method loco needs --loco-file!" << std::endl;
+        return false;
     }
     if (!o.trait_file.empty()) {
         const char* why = o.run_mode != "association_test" ? "needs --run-mode association_test"

@@ -51,6 +51,7 @@ struct Options {
     // line of F: <name> <phen-file> <estimate-file>.  Stands instead of
     // --phen-file / --estimate-file
     std::string trait_file;
+    std::string loco_file;  // --pval-method loco: one label per marker (vio::read_labels)
 };
 
 // Parses argv exactly like Options::read_command_line_options + check_options:
