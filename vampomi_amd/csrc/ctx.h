@@ -1,4 +1,4 @@
-// ctx.h — libvampomi internals shared by engine.cpp, pcg.cpp and vamp.cpp.
+// ctx.h — libvampomi internals shared by engine.cpp, ingest.cpp, pcg.cpp and vamp.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -97,7 +97,7 @@ struct vampomi_ctx {
     // the ranks agree on nothing that depends on it)
     void* X = nullptr;
     int storage = VAMPOMI_STORE_F64;
-    // U16 storage: what the last load's quantisation saw (vk::quantise_cols;
+    // U16 storage: what the last load's quantisation saw (vk::convert_cols;
     // zeroed when a load starts) and its host copy (vampomi_get_quant_stats)
     vk::QuantRec* qrec = nullptr;
     int64_t q_clamped = 0;
@@ -113,25 +113,19 @@ struct vampomi_ctx {
     std::vector<int64_t> na_per_marker;  // empty: all zeros
     // the row subset (vampomi_set_row_subset; N_file == 0: none): the files hold
     // N_file rows of which rows_host (N ascending indices) are loaded; rows_dev:
-    // their device copy for vk::gather_cols
+    // their device copy for vk::convert_cols
     int64_t N_file = 0;
     std::vector<int64_t> rows_host;
     int32_t* rows_dev = nullptr;
     // covariate adjustment (vampomi_set_adjust; adj_R == 0: none; fixed once X is
     // allocated): adj_Q, N x adj_R orthonormal doubles, column-major, the
-    // intercept's first; adj_dropped, one flag per column of the table.  During
-    // a load only (adjust_begin .. adjust_end, engine.cpp): the device copy of
-    // Q, put_cols' fp64 work block, and the absorbed flags and counter that
-    // vk::adjust_cols fills; adj_flags / adj_absorbed are their host copy
-    // (vampomi_get_adjust_stats)
+    // intercept's first; adj_dropped, one flag per column of the table.  The
+    // device side exists during a load only (IngestScope, ingest.cpp);
+    // adj_flags / adj_absorbed are the host copy of what vk::adjust_cols
+    // recorded (vampomi_get_adjust_stats)
     int adj_R = 0, adj_C = 0;
     std::vector<double> adj_Q;
     std::vector<int> adj_dropped;
-    double* adj_Qdev = nullptr;
-    double* adj_work = nullptr;
-    size_t adj_work_cap = 0;  // bytes
-    uint8_t* adj_flags_dev = nullptr;
-    unsigned long long* adj_cnt_dev = nullptr;
     std::vector<uint8_t> adj_flags;  // empty: all zeros
     int64_t adj_absorbed = 0;
     double* mave = nullptr;
@@ -263,6 +257,11 @@ TimedLaunch launch_stat(vampomi_ctx* c, int cls, int K, double bytes, double flo
 // (the gated launches of a CG step queued after the solve had stopped)
 void drop_launches(vampomi_ctx* c, size_t pending_mark, const vampomi_stats& before);
 void release_ctx_resources(vampomi_ctx* c);
+// ---- ingest (ingest.cpp) ------------------------------------------------------
+// the rows of a column of the input: the file's with a row subset, else N
+int64_t rows_in(const vampomi_ctx* c);
+// y <- y - Q (Q^T y) on an adjusted context, long double sums, rounded once
+void adjust_phen(const vampomi_ctx* c, std::vector<double>& y);
 
 // ---- operators on device buffers ---------------------------------------------
 // out_k = A x_k (K <= 4), outputs at outbase + k*ld (one all-reduce). COLLECTIVE

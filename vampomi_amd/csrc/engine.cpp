@@ -11,7 +11,6 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cfloat>
 #include <chrono>
 #include <condition_variable>
@@ -25,9 +24,6 @@
 #include <string>
 #include <thread>
 #include <vector>
-
-#include <fcntl.h>
-#include <unistd.h>
 
 #include "ctx.h"
 #include "hostio.h"
@@ -1311,705 +1307,8 @@ extern "C" vampomi_status vampomi_barrier_timeout(vampomi_ctx* c, double seconds
 }
 
 // ---------------------------------------------------------------------------
-// data ingest
+// the phenotype (the methylation ingest: ingest.cpp)
 // ---------------------------------------------------------------------------
-static vampomi_status ensure_X(vampomi_ctx* c) {
-    if (c->X) return VAMPOMI_OK;
-    const size_t bytes = (size_t)std::max<int64_t>(c->M, 1) * (size_t)c->ld * (size_t)c->esize();
-    const hipError_t e = hipMalloc(&c->X, bytes);
-    if (e != hipSuccess)
-        return fail(VAMPOMI_ERR_OOM, "hipMalloc(" + std::to_string(bytes) + " B): " + hipGetErrorString(e));
-    return VAMPOMI_OK;
-}
-
-extern "C" vampomi_status vampomi_set_storage(vampomi_ctx* c, int storage) {
-    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
-    if (storage != VAMPOMI_STORE_F64 && storage != VAMPOMI_STORE_F32 && storage != VAMPOMI_STORE_U16)
-        return fail(VAMPOMI_ERR_ARG, "storage must be VAMPOMI_STORE_F64, VAMPOMI_STORE_F32 or VAMPOMI_STORE_U16");
-    if (c->X) return fail(VAMPOMI_ERR_STATE, "the storage is fixed once the methylation shard is allocated");
-    if (storage == VAMPOMI_STORE_U16 && c->adj_R)
-        return fail(VAMPOMI_ERR_ARG, "covariate-adjusted values leave [0, 1]: VAMPOMI_STORE_U16 cannot hold them");
-    c->storage = storage;
-    return VAMPOMI_OK;
-}
-
-extern "C" vampomi_status vampomi_get_storage(const vampomi_ctx* c, int* storage) {
-    if (!c || !storage) return fail(VAMPOMI_ERR_ARG, "null argument");
-    *storage = c->storage;
-    return VAMPOMI_OK;
-}
-
-extern "C" vampomi_status vampomi_set_meth_na(vampomi_ctx* c, int policy, double max_missing_frac) {
-    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
-    if (policy != VAMPOMI_NA_PASS && policy != VAMPOMI_NA_FATAL && policy != VAMPOMI_NA_MEAN)
-        return fail(VAMPOMI_ERR_ARG, "the policy must be VAMPOMI_NA_PASS, VAMPOMI_NA_FATAL or VAMPOMI_NA_MEAN");
-    if (!(max_missing_frac >= 0.0 && max_missing_frac <= 1.0))
-        return fail(VAMPOMI_ERR_ARG, "max_missing_frac must lie in [0, 1]");
-    if (c->X) return fail(VAMPOMI_ERR_STATE, "the NaN policy is fixed once the methylation shard is allocated");
-    c->na_policy = policy;
-    c->na_max_frac = max_missing_frac;
-    return VAMPOMI_OK;
-}
-
-extern "C" vampomi_status vampomi_get_meth_na(const vampomi_ctx* c, int* policy, double* max_missing_frac) {
-    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
-    if (policy) *policy = c->na_policy;
-    if (max_missing_frac) *max_missing_frac = c->na_max_frac;
-    return VAMPOMI_OK;
-}
-
-extern "C" vampomi_status vampomi_set_row_subset(vampomi_ctx* c, int64_t N_file, const int64_t* rows, int64_t n) {
-    if (!c || !rows) return fail(VAMPOMI_ERR_ARG, "null argument");
-    if (c->X) return fail(VAMPOMI_ERR_STATE, "the row subset is fixed once the methylation shard is allocated");
-    if (c->have_y || c->cov_C > 0)
-        return fail(VAMPOMI_ERR_STATE, "set the row subset before the phenotype and the covariates");
-    if (c->adj_R) return fail(VAMPOMI_ERR_STATE, "set the row subset before the covariate adjustment");
-    if (N_file >= ((int64_t)1 << 31)) return fail(VAMPOMI_ERR_ARG, "row subset: N_file must be below 2^31");
-    if (n != c->N)
-        return fail(VAMPOMI_ERR_ARG, "row subset: n (" + std::to_string(n) + ") != the context's N (" +
-                                         std::to_string(c->N) + "): open the context with N = n");
-    if (n < 2 || n > N_file) return fail(VAMPOMI_ERR_ARG, "row subset: 2 <= n <= N_file");
-    for (int64_t j = 0; j < n; ++j)
-        if (rows[j] < 0 || rows[j] >= N_file || (j > 0 && rows[j] <= rows[j - 1]))
-            return fail(VAMPOMI_ERR_ARG, "row subset: rows must be strictly ascending within [0, N_file) (entry " +
-                                             std::to_string(j) + " is " + std::to_string(rows[j]) + ")");
-    HIPCHK(hipSetDevice(c->device));
-    if (!c->rows_dev && hipMalloc((void**)&c->rows_dev, (size_t)n * sizeof(int32_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        c->rows_dev = nullptr;
-        return fail(VAMPOMI_ERR_OOM, "row subset");
-    }
-    const std::vector<int32_t> r32(rows, rows + n);
-    HIPCHK(hipMemcpyAsync(c->rows_dev, r32.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    c->rows_host.assign(rows, rows + n);
-    c->N_file = N_file;
-    return VAMPOMI_OK;
-}
-
-extern "C" vampomi_status vampomi_get_row_subset(const vampomi_ctx* c, int64_t* N_file, int64_t* rows) {
-    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
-    if (N_file) *N_file = c->N_file;
-    if (rows && c->N_file) std::memcpy(rows, c->rows_host.data(), c->rows_host.size() * sizeof(int64_t));
-    return VAMPOMI_OK;
-}
-
-// the rows of a column of the input: the file's with a row subset, else N
-static int64_t rows_in(const vampomi_ctx* c) { return c->N_file ? c->N_file : c->N; }
-
-// ---------------------------------------------------------------------------
-// covariate adjustment of the linear model: X and y are
-// replaced at ingest by their residuals on span{1, Z}
-// ---------------------------------------------------------------------------
-// Modified Gram-Schmidt over the intercept, then Z's columns in order: each
-// vector is orthogonalised twice against the accepted ones, every sum in long
-// double, and rounded to double once it is normalised.  A column whose norm is
-// 0, or at most 1e-8 of it after the orthogonalisation, is dropped.
-extern "C" vampomi_status vampomi_adjust_basis(const double* Z, int64_t n, int C, int64_t ld_in, double* Q, int* R,
-                                               int* dropped) {
-    if (C < 0 || C > VAMPOMI_MAX_C)
-        return fail(VAMPOMI_ERR_ARG, "number of covariates out of range (0.." + std::to_string(VAMPOMI_MAX_C) + ")");
-    if (n < 1 || !Q || !R || (C > 0 && (!Z || !dropped || ld_in < n))) return fail(VAMPOMI_ERR_ARG, "bad covariate table");
-    for (int i = 0; i < C; ++i)
-        for (int64_t j = 0; j < n; ++j)
-            if (!std::isfinite(Z[(int64_t)i * ld_in + j]))
-                return fail(VAMPOMI_ERR_ARG, "covariate " + std::to_string(i) + ", row " + std::to_string(j) +
-                                                 " is not finite");
-    std::vector<long double> v((size_t)n);
-    const auto norm = [&] {
-        long double s = 0.0L;
-        for (int64_t j = 0; j < n; ++j) s += v[(size_t)j] * v[(size_t)j];
-        return std::sqrt(s);
-    };
-    int r = 0;
-    for (int i = -1; i < C; ++i) {  // -1: the intercept
-        for (int64_t j = 0; j < n; ++j) v[(size_t)j] = i < 0 ? 1.0L : (long double)Z[(int64_t)i * ld_in + j];
-        const long double before = norm();
-        bool keep = before > 0.0L;
-        if (keep) {
-            for (int pass = 0; pass < 2; ++pass)
-                for (int k = 0; k < r; ++k) {
-                    const double* q = Q + (size_t)k * (size_t)n;
-                    long double d = 0.0L;
-                    for (int64_t j = 0; j < n; ++j) d += (long double)q[j] * v[(size_t)j];
-                    for (int64_t j = 0; j < n; ++j) v[(size_t)j] -= d * (long double)q[j];
-                }
-            const long double after = norm();
-            keep = after > 1e-8L * before;
-            if (keep) {
-                double* q = Q + (size_t)r * (size_t)n;
-                for (int64_t j = 0; j < n; ++j) q[j] = (double)(v[(size_t)j] / after);
-                ++r;
-            }
-        }
-        if (i >= 0) dropped[i] = keep ? 0 : 1;
-    }
-    *R = r;
-    return VAMPOMI_OK;
-}
-
-extern "C" vampomi_status vampomi_set_adjust(vampomi_ctx* c, const double* Z, int C, int64_t ld_in) {
-    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
-    if (C < 0 || C > VAMPOMI_MAX_C)
-        return fail(VAMPOMI_ERR_ARG, "number of covariates out of range (0.." + std::to_string(VAMPOMI_MAX_C) + ")");
-    if (C > 0 && (!Z || ld_in < c->N)) return fail(VAMPOMI_ERR_ARG, "bad covariate table");
-    if (c->u16())
-        return fail(VAMPOMI_ERR_ARG, "covariate-adjusted values leave [0, 1]: VAMPOMI_STORE_U16 cannot hold them");
-    if (c->X) return fail(VAMPOMI_ERR_STATE, "the adjustment is fixed once the methylation shard is allocated");
-    if (c->have_y) return fail(VAMPOMI_ERR_STATE, "set the adjustment before the phenotype");
-    std::vector<double> Q((size_t)(C + 1) * (size_t)c->N);
-    std::vector<int> dropped((size_t)C, 0);
-    int R = 0;
-    STCHK(vampomi_adjust_basis(Z, c->N, C, ld_in, Q.data(), &R, dropped.data()));
-    Q.resize((size_t)R * (size_t)c->N);
-    c->adj_Q.swap(Q);
-    c->adj_dropped.swap(dropped);
-    c->adj_R = R;
-    c->adj_C = C;
-    return VAMPOMI_OK;
-}
-
-extern "C" vampomi_status vampomi_read_adjust(vampomi_ctx* c, const char* path, int C) {
-    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
-    if (C < 0 || C > VAMPOMI_MAX_C)
-        return fail(VAMPOMI_ERR_ARG, "number of covariates out of range (0.." + std::to_string(VAMPOMI_MAX_C) + ")");
-    if (C == 0) return vampomi_set_adjust(c, nullptr, 0, c->N);
-    const int64_t Nin = c->N_file ? c->N_file : c->N;
-    std::vector<double> raw((size_t)C * (size_t)Nin);
-    STCHK(vampomi_parse_covariates(path, Nin, C, 0, raw.data()));
-    if (!c->N_file) return vampomi_set_adjust(c, raw.data(), C, c->N);
-    std::vector<double> Z((size_t)C * (size_t)c->N);
-    for (int j = 0; j < C; ++j)
-        for (int64_t i = 0; i < c->N; ++i)
-            Z[(size_t)j * c->N + i] = raw[(size_t)j * c->N_file + c->rows_host[(size_t)i]];
-    return vampomi_set_adjust(c, Z.data(), C, c->N);
-}
-
-extern "C" vampomi_status vampomi_get_adjust(const vampomi_ctx* c, int* R, int* dropped, double* Q) {
-    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
-    if (R) *R = c->adj_R;
-    if (dropped) std::copy(c->adj_dropped.begin(), c->adj_dropped.end(), dropped);
-    if (Q && c->adj_R) std::memcpy(Q, c->adj_Q.data(), c->adj_Q.size() * sizeof(double));
-    return VAMPOMI_OK;
-}
-
-extern "C" vampomi_status vampomi_get_adjust_stats(const vampomi_ctx* c, int64_t* absorbed, uint8_t* per_marker) {
-    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
-    if (!c->have_X) return fail(VAMPOMI_ERR_STATE, "no methylation data loaded");
-    if (absorbed) *absorbed = c->adj_absorbed;
-    if (per_marker && c->adj_flags.empty()) std::fill(per_marker, per_marker + c->M, (uint8_t)0);
-    if (per_marker && !c->adj_flags.empty()) std::copy(c->adj_flags.begin(), c->adj_flags.end(), per_marker);
-    return VAMPOMI_OK;
-}
-
-// y <- y - Q (Q^T y) on an adjusted context, long double sums, rounded once
-static void adjust_phen(const vampomi_ctx* c, std::vector<double>& y) {
-    if (!c->adj_R) return;
-    const size_t n = (size_t)c->N;
-    std::vector<long double> r(y.begin(), y.end());
-    for (int k = 0; k < c->adj_R; ++k) {
-        const double* q = c->adj_Q.data() + (size_t)k * n;
-        long double d = 0.0L;
-        for (size_t j = 0; j < n; ++j) d += (long double)q[j] * (long double)y[j];
-        for (size_t j = 0; j < n; ++j) r[j] -= d * (long double)q[j];
-    }
-    for (size_t j = 0; j < n; ++j) y[j] = (double)r[j];
-}
-
-// The device side of an adjusted load: Q, the absorbed flags and the counter
-// from adjust_begin (after ensure_X) and put_cols' work block live until
-// adjust_free, which every exit path of a load reaches (AdjustLoad).  Without
-// an adjustment nothing is allocated and nothing is launched.
-static void adjust_free(vampomi_ctx* c) {
-    if (!c->adj_Qdev && !c->adj_work && !c->adj_flags_dev && !c->adj_cnt_dev) return;
-    (void)hipStreamSynchronize(c->st);
-    if (c->adj_Qdev) (void)hipFree(c->adj_Qdev);
-    if (c->adj_work) (void)hipFree(c->adj_work);
-    if (c->adj_flags_dev) (void)hipFree(c->adj_flags_dev);
-    if (c->adj_cnt_dev) (void)hipFree(c->adj_cnt_dev);
-    c->adj_Qdev = c->adj_work = nullptr;
-    c->adj_flags_dev = nullptr;
-    c->adj_cnt_dev = nullptr;
-    c->adj_work_cap = 0;
-}
-
-struct AdjustLoad {
-    vampomi_ctx* c;
-    ~AdjustLoad() { adjust_free(c); }
-};
-
-static vampomi_status adjust_begin(vampomi_ctx* c) {
-    c->adj_absorbed = 0;
-    c->adj_flags.clear();
-    if (!c->adj_R) return VAMPOMI_OK;
-    const size_t qb = c->adj_Q.size() * sizeof(double), fb = (size_t)std::max<int64_t>(c->M, 1);
-    if (hipMalloc((void**)&c->adj_Qdev, qb) != hipSuccess || hipMalloc((void**)&c->adj_flags_dev, fb) != hipSuccess ||
-        hipMalloc((void**)&c->adj_cnt_dev, sizeof(unsigned long long)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(VAMPOMI_ERR_OOM, "covariate basis on the device");
-    }
-    HIPCHK(hipMemcpyAsync(c->adj_Qdev, c->adj_Q.data(), qb, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipMemsetAsync(c->adj_flags_dev, 0, fb, c->st));
-    HIPCHK(hipMemsetAsync(c->adj_cnt_dev, 0, sizeof(unsigned long long), c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    return VAMPOMI_OK;
-}
-
-static vampomi_status adjust_end(vampomi_ctx* c) {
-    if (!c->adj_R) return VAMPOMI_OK;
-    unsigned long long n = 0;
-    c->adj_flags.assign((size_t)c->M, 0);
-    HIPCHK(hipMemcpyAsync(&n, c->adj_cnt_dev, sizeof n, hipMemcpyDeviceToHost, c->st));
-    if (c->M > 0)
-        HIPCHK(hipMemcpyAsync(c->adj_flags.data(), c->adj_flags_dev, (size_t)c->M, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    c->adj_absorbed = (int64_t)n;
-    return VAMPOMI_OK;
-}
-
-static vampomi_status finish_X(vampomi_ctx* c) {
-    const size_t es = (size_t)c->esize();
-    if (c->ld > c->N && c->M > 0)
-        HIPCHK(hipMemset2DAsync((char*)c->X + (size_t)c->N * es, (size_t)c->ld * es, 0, (size_t)(c->ld - c->N) * es,
-                                (size_t)c->M, c->st));
-    // compute_markers_statistics with nonas = N (read_phen asserts N rows, src/data.cpp:85)
-    HIPCHK(vk::marker_stats(c->shard(), (double)c->N, c->alpha_scale, c->mave, c->msig, c->st));
-    STCHK(sync_stream(c, c->st));
-    c->have_X = true;
-    return VAMPOMI_OK;
-}
-
-// the bytes of one staging chunk of an ingest (256 MB; VAMPOMI_IO_CHUNK_BYTES:
-// tuning experiments, and tests of the chunk boundaries at small shapes)
-static int64_t io_chunk_bytes() {
-    const char* env = std::getenv("VAMPOMI_IO_CHUNK_BYTES");
-    const int64_t v = env ? std::atoll(env) : 0;
-    return v >= 4096 ? v : (int64_t)256 << 20;
-}
-
-// U16 storage: a load starts with the quantisation record zeroed (and the host
-// copy of the last one forgotten)
-static vampomi_status quant_begin(vampomi_ctx* c) {
-    c->q_clamped = 0;
-    c->q_max_err = 0.0;
-    if (!c->u16()) return VAMPOMI_OK;
-    if (!c->qrec && hipMalloc((void**)&c->qrec, sizeof(vk::QuantRec)) != hipSuccess) {
-        (void)hipGetLastError();
-        c->qrec = nullptr;
-        return fail(VAMPOMI_ERR_OOM, "quantisation record");
-    }
-    HIPCHK(hipMemsetAsync(c->qrec, 0, sizeof(vk::QuantRec), c->st));
-    HIPCHK(hipMemsetAsync(&c->qrec->first, 0xff, sizeof(unsigned long long), c->st));
-    return VAMPOMI_OK;
-}
-
-// ... and ends with the record read: rejected entries fail the load with
-// VAMPOMI_ERR_RANGE and leave the context without X
-static vampomi_status quant_end(vampomi_ctx* c) {
-    if (!c->u16() || !c->qrec) return VAMPOMI_OK;
-    vk::QuantRec r{};
-    HIPCHK(hipMemcpyAsync(&r, c->qrec, sizeof r, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    if (r.rejected) {
-        c->have_X = false;
-        const long long marker = (long long)(r.first / (unsigned long long)rows_in(c));
-        const long long row = (long long)(r.first % (unsigned long long)rows_in(c));  // (the file's row)
-        return fail(VAMPOMI_ERR_RANGE,
-                    std::to_string(r.rejected) + " methylation value(s) cannot be stored as 16-bit fixed point (NaN, "
-                    "infinite, below 0 or above 1); the first is marker " + std::to_string(marker) + ", row " +
-                    std::to_string(row));
-    }
-    c->q_clamped = (int64_t)r.clamped;
-    std::memcpy(&c->q_max_err, &r.max_err, sizeof(double));
-    return VAMPOMI_OK;
-}
-
-// whether a load of elements of in_es bytes looks for missing values: a policy
-// other than pass, and an input that can hold a NaN
-static bool na_active(const vampomi_ctx* c, int in_es) { return c->na_policy != VAMPOMI_NA_PASS && in_es != 2; }
-
-// A load starts with the missing-value counts forgotten and, where it will
-// look (look: na_active), the device record and the per-marker counters zeroed
-static vampomi_status na_begin(vampomi_ctx* c, bool look) {
-    c->na_missing = c->na_markers = c->na_masked = 0;
-    c->na_per_marker.clear();
-    if (!look) return VAMPOMI_OK;
-    const size_t cb = (size_t)std::max<int64_t>(c->M, 1) * sizeof(int64_t);
-    if ((!c->na_rec && hipMalloc((void**)&c->na_rec, sizeof(vk::NaRec)) != hipSuccess) ||
-        (!c->na_cnt && hipMalloc((void**)&c->na_cnt, cb) != hipSuccess)) {
-        (void)hipGetLastError();
-        return fail(VAMPOMI_ERR_OOM, "missing-value counters");
-    }
-    HIPCHK(hipMemsetAsync(c->na_rec, 0, sizeof(vk::NaRec), c->st));
-    HIPCHK(hipMemsetAsync(&c->na_rec->first, 0xff, sizeof(unsigned long long), c->st));
-    HIPCHK(hipMemsetAsync(c->na_cnt, 0, cb, c->st));
-    return VAMPOMI_OK;
-}
-
-// ... and ends with the record read (before quant_end: of a NaN and a value
-// out of range the NaN is reported): under VAMPOMI_NA_FATAL missing entries
-// fail the load with VAMPOMI_ERR_NAN_METH and leave the context without X
-static vampomi_status na_end(vampomi_ctx* c, bool look) {
-    if (!look) return VAMPOMI_OK;
-    vk::NaRec r{};
-    HIPCHK(hipMemcpyAsync(&r, c->na_rec, sizeof r, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    if (r.missing && c->na_policy == VAMPOMI_NA_FATAL) {
-        c->have_X = false;
-        const long long marker = (long long)(r.first / (unsigned long long)rows_in(c));
-        const long long row = (long long)(r.first % (unsigned long long)rows_in(c));  // (the file's row)
-        return fail(VAMPOMI_ERR_NAN_METH, std::to_string(r.missing) + " missing methylation value(s) (NaN); the first "
-                                          "is marker " + std::to_string(marker) + ", row " + std::to_string(row));
-    }
-    if (r.missing) {
-        c->na_per_marker.resize((size_t)c->M);
-        HIPCHK(hipMemcpyAsync(c->na_per_marker.data(), c->na_cnt, (size_t)c->M * sizeof(int64_t),
-                              hipMemcpyDeviceToHost, c->st));
-        HIPCHK(hipStreamSynchronize(c->st));
-    }
-    c->na_missing = (int64_t)r.missing;
-    c->na_markers = (int64_t)r.markers;
-    c->na_masked = (int64_t)r.masked;
-    return VAMPOMI_OK;
-}
-
-extern "C" vampomi_status vampomi_get_missing_stats(const vampomi_ctx* c, int64_t* missing,
-                                                    int64_t* markers_with_missing, int64_t* markers_masked,
-                                                    int64_t* per_marker) {
-    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
-    if (!c->have_X) return fail(VAMPOMI_ERR_STATE, "no methylation data loaded");
-    if (missing) *missing = c->na_missing;
-    if (markers_with_missing) *markers_with_missing = c->na_markers;
-    if (markers_masked) *markers_masked = c->na_masked;
-    if (per_marker && c->na_per_marker.empty()) std::fill(per_marker, per_marker + c->M, (int64_t)0);
-    if (per_marker && !c->na_per_marker.empty())
-        std::copy(c->na_per_marker.begin(), c->na_per_marker.end(), per_marker);
-    return VAMPOMI_OK;
-}
-
-extern "C" vampomi_status vampomi_get_quant_stats(const vampomi_ctx* c, int64_t* clamped, double* max_abs_err) {
-    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
-    if (!c->have_X) return fail(VAMPOMI_ERR_STATE, "no methylation data loaded");
-    if (clamped) *clamped = c->q_clamped;
-    if (max_abs_err) *max_abs_err = c->q_max_err;
-    return VAMPOMI_OK;
-}
-
-// Columns [i0, i0 + nc) of the shard from a host block of nc columns of
-// elements of in_es bytes (8: doubles, 4: floats, 2: 16-bit fixed point),
-// column stride ld_in elements.  The same element type as the storage: a
-// strided copy into the padded layout.  Otherwise the block is staged on the
-// device as it is and converted there (vk::narrow_cols, nearest even /
-// vk::widen_cols and vk::dequant_cols, exact / vk::quantise_cols, nearest even
-// on the 2^-16 grid, range-checked into c->qrec):
-// *stage (cap_bytes; grown as needed, freed by the caller) is that buffer.  All
-// on the context's stream, so the caller may reuse src once the stream has
-// passed this point.  With a row subset the block's columns hold N_file
-// elements and every block takes the staging hop: vk::gather_cols keeps the
-// subset's rows as it converts (or copies).  Under a NaN policy other than
-// pass every block of doubles or floats takes the staging hop too, and
-// vk::na_ingest_cols does the conversion, the gather and the policy's work.
-static vampomi_status put_cols(vampomi_ctx* c, int64_t i0, int64_t nc, const void* src, int64_t ld_in, int in_es,
-                               void** stage, size_t* cap_bytes) {
-    if (nc <= 0) return VAMPOMI_OK;
-    const size_t es = (size_t)c->esize();
-    char* dst = (char*)c->X + (size_t)i0 * (size_t)c->ld * es;
-    // An adjusted context: the same conversions, pointed at an fp64 work block
-    // of packed columns (the row gather and the NaN fill come first), which
-    // vk::adjust_cols then empties into the shard: one rounding into F32.
-    double* work = nullptr;
-    if (c->adj_R) {
-        const size_t wb = (size_t)nc * (size_t)c->N * 8;
-        if (c->adj_work_cap < wb) {
-            HIPCHK(hipStreamSynchronize(c->st));
-            if (c->adj_work) (void)hipFree(c->adj_work);
-            c->adj_work = nullptr;
-            c->adj_work_cap = 0;
-            if (hipMalloc((void**)&c->adj_work, wb) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(VAMPOMI_ERR_OOM, "device work block of the covariate adjustment");
-            }
-            c->adj_work_cap = wb;
-        }
-        work = c->adj_work;
-    }
-    const auto adjust = [&]() -> vampomi_status {
-        HIPCHK(vk::adjust_cols(work, c->N, nc, c->adj_Qdev, c->adj_R, dst, c->ek(), c->ld, c->adj_flags_dev + i0,
-                               c->adj_cnt_dev, c->st));
-        return VAMPOMI_OK;
-    };
-    if (work && in_es == 8 && !c->N_file && !na_active(c, in_es)) {  // doubles as they are: no staging hop
-        HIPCHK(hipMemcpy2DAsync(work, (size_t)c->N * 8, src, (size_t)ld_in * 8, (size_t)c->N * 8, (size_t)nc,
-                                hipMemcpyHostToDevice, c->st));
-        return adjust();
-    }
-    if (!work && (size_t)in_es == es && !c->N_file && !na_active(c, in_es)) {
-        HIPCHK(hipMemcpy2DAsync(dst, (size_t)c->ld * es, src, (size_t)ld_in * es, (size_t)c->N * es, (size_t)nc,
-                                hipMemcpyHostToDevice, c->st));
-        return VAMPOMI_OK;
-    }
-    const int64_t Nin = rows_in(c);
-    const size_t need = (size_t)nc * (size_t)Nin * (size_t)in_es;
-    if (*cap_bytes < need) {
-        HIPCHK(hipStreamSynchronize(c->st));
-        if (*stage) (void)hipFree(*stage);
-        *stage = nullptr;
-        *cap_bytes = 0;
-        if (hipMalloc(stage, need) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(VAMPOMI_ERR_OOM, "device staging buffer of the storage conversion");
-        }
-        *cap_bytes = need;
-    }
-    HIPCHK(hipMemcpy2DAsync(*stage, (size_t)Nin * in_es, src, (size_t)ld_in * in_es, (size_t)Nin * in_es,
-                            (size_t)nc, hipMemcpyHostToDevice, c->st));
-    if (work) {
-        const int sek = in_es == 2 ? vk::kXU16 : in_es == 4 ? vk::kXF32 : vk::kXF64;
-        if (na_active(c, in_es))
-            HIPCHK(vk::na_ingest_cols(*stage, sek, Nin, c->rows_dev, c->N, nc, work, vk::kXF64, c->N, Nin, c->S + i0,
-                                      c->na_policy, c->na_max_frac, c->na_cnt + i0, c->na_rec, nullptr, c->st));
-        else if (c->N_file)
-            HIPCHK(vk::gather_cols(*stage, sek, Nin, c->rows_dev, c->N, nc, work, vk::kXF64, c->N, Nin, c->S + i0,
-                                   nullptr, c->st));
-        else if (in_es == 2)
-            HIPCHK(vk::dequant_cols((const uint16_t*)*stage, c->N, c->N, nc, work, c->N, c->st));
-        else
-            HIPCHK(vk::widen_cols((const float*)*stage, c->N, c->N, nc, work, c->N, c->st));
-        return adjust();
-    }
-    if (na_active(c, in_es))
-        HIPCHK(vk::na_ingest_cols(*stage, in_es == 4 ? vk::kXF32 : vk::kXF64, Nin, c->rows_dev, c->N, nc, dst, c->ek(),
-                                  c->ld, Nin, c->S + i0, c->na_policy, c->na_max_frac, c->na_cnt + i0, c->na_rec,
-                                  c->qrec, c->st));
-    else if (c->N_file)
-        HIPCHK(vk::gather_cols(*stage, in_es == 2 ? vk::kXU16 : in_es == 4 ? vk::kXF32 : vk::kXF64, Nin, c->rows_dev,
-                               c->N, nc, dst, c->ek(), c->ld, Nin, c->S + i0, c->qrec, c->st));
-    else if (es == 2 && in_es == 8)
-        HIPCHK(vk::quantise_cols((const double*)*stage, c->N, c->N, nc, (uint16_t*)dst, c->ld, c->S + i0, c->qrec,
-                                 c->st));
-    else if (es == 2)
-        HIPCHK(vk::quantise_cols((const float*)*stage, c->N, c->N, nc, (uint16_t*)dst, c->ld, c->S + i0, c->qrec,
-                                 c->st));
-    else if (in_es == 2 && es == 8)
-        HIPCHK(vk::dequant_cols((const uint16_t*)*stage, c->N, c->N, nc, (double*)dst, c->ld, c->st));
-    else if (in_es == 2)
-        HIPCHK(vk::dequant_cols((const uint16_t*)*stage, c->N, c->N, nc, (float*)dst, c->ld, c->st));
-    else if (in_es == 8)
-        HIPCHK(vk::narrow_cols((const double*)*stage, c->N, c->N, nc, (float*)dst, c->ld, c->st));
-    else
-        HIPCHK(vk::widen_cols((const float*)*stage, c->N, c->N, nc, (double*)dst, c->ld, c->st));
-    return VAMPOMI_OK;
-}
-
-// a host shard of doubles (in_es 8), floats (4) or 16-bit fixed point (2), in
-// chunks of about 256 MB where it has to be converted (put_cols' staging
-// buffer)
-static vampomi_status load_host(vampomi_ctx* c, const void* X, int64_t ld_in, int in_es) {
-    if (!c || (!X && c->M > 0) || ld_in < rows_in(c)) return fail(VAMPOMI_ERR_ARG, "invalid host shard");
-    HIPCHK(hipSetDevice(c->device));
-    STCHK(ensure_X(c));
-    STCHK(quant_begin(c));
-    const bool look = na_active(c, in_es);
-    STCHK(na_begin(c, look));
-    AdjustLoad adj_{c};
-    STCHK(adjust_begin(c));
-    void* stage = nullptr;
-    size_t cap = 0;
-    vampomi_status st = VAMPOMI_OK;
-    const int64_t chunk = (int64_t)in_es == c->esize() && !c->N_file && !look && !c->adj_R
-                              ? std::max<int64_t>(c->M, 1)
-                              : std::max<int64_t>(1, io_chunk_bytes() / (rows_in(c) * in_es));
-    for (int64_t i0 = 0; i0 < c->M && st == VAMPOMI_OK; i0 += chunk)
-        st = put_cols(c, i0, std::min(chunk, c->M - i0), (const char*)X + (size_t)i0 * (size_t)ld_in * in_es, ld_in,
-                      in_es, &stage, &cap);
-    if (stage) {
-        (void)hipStreamSynchronize(c->st);
-        (void)hipFree(stage);
-    }
-    if (st != VAMPOMI_OK) return st;
-    STCHK(na_end(c, look));
-    STCHK(quant_end(c));
-    STCHK(adjust_end(c));
-    return finish_X(c);
-}
-
-extern "C" vampomi_status vampomi_load_meth_host(vampomi_ctx* c, const double* X, int64_t ld_in) {
-    return load_host(c, X, ld_in, 8);
-}
-
-extern "C" vampomi_status vampomi_load_meth_host_u16(vampomi_ctx* c, const uint16_t* X, int64_t ld_in) {
-    return load_host(c, X, ld_in, 2);
-}
-
-extern "C" vampomi_status vampomi_load_meth_host_f32(vampomi_ctx* c, const float* X, int64_t ld_in) {
-    return load_host(c, X, ld_in, 4);
-}
-
-// [off, off + want) of fd into dst, split over nt reader threads (page cache
-// and NVMe both need several requests in flight to stream at full rate)
-static bool pread_parallel(int fd, char* dst, size_t want, off_t off, int nt) {
-    if (nt <= 1 || want < ((size_t)8 << 20)) nt = 1;
-    const size_t per = ((want + nt - 1) / nt + 4095) & ~(size_t)4095;
-    std::atomic<bool> ok{true};
-    auto work = [&](size_t lo, size_t hi) {
-        size_t got = 0;
-        while (lo + got < hi) {
-            const ssize_t r = ::pread(fd, dst + lo + got, hi - lo - got, off + (off_t)(lo + got));
-            if (r <= 0) {
-                ok = false;
-                return;
-            }
-            got += (size_t)r;
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; ++t) {
-        const size_t lo = (size_t)t * per;
-        if (lo < want) th.emplace_back(work, lo, std::min(want, lo + per));
-    }
-    work(0, std::min(want, per));
-    for (auto& x : th) x.join();
-    return ok;
-}
-
-// read_methylation_data (src/data.cpp:116-153): this rank's M*N elements of
-// in_es bytes (8: the reference's doubles; 4: floats, 2: little-endian uint16
-// k meaning k * 2^-16, in the same marker-major layout) at byte offset
-// S*N*in_es (64-bit offsets: the reference's int i*N
-// overflows past 2^31 elements), streamed through three pinned 256 MB staging
-// buffers: the parallel read of chunk k+1 overlaps the host-to-device copy of
-// chunk k, which lands directly in the ld-padded column layout, or, where the
-// file's element type is not the storage's, in a device staging buffer that a
-// conversion kernel empties into it (put_cols).  Marker statistics follow on
-// the device (finish_X).
-static vampomi_status load_file(vampomi_ctx* c, const char* path, int in_es) {
-    if (!c || !path) return fail(VAMPOMI_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(c->device));
-    int fd = ::open(path, O_RDONLY);
-    if (fd < 0) return fail(VAMPOMI_ERR_IO, std::string("cannot open methylation file ") + path);
-    if (const vampomi_status s0 = ensure_X(c)) {
-        ::close(fd);
-        return s0;
-    }
-    if (const vampomi_status s0 = quant_begin(c)) {
-        ::close(fd);
-        return s0;
-    }
-    const bool look = na_active(c, in_es);
-    if (const vampomi_status s0 = na_begin(c, look)) {
-        ::close(fd);
-        return s0;
-    }
-    AdjustLoad adj_{c};
-    if (const vampomi_status s0 = adjust_begin(c)) {
-        ::close(fd);
-        return s0;
-    }
-    const size_t colb = (size_t)rows_in(c) * (size_t)in_es;
-    const size_t chunk_cols = std::max<size_t>(1, (size_t)io_chunk_bytes() / colb);
-    const char* env = std::getenv("VAMPOMI_IO_THREADS");
-    const int nt = env ? std::max(1, std::atoi(env)) : (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
-    constexpr int NB = 3;
-    char* pin[NB] = {};
-    hipEvent_t done[NB];
-    bool used[NB] = {};
-    for (int b = 0; b < NB; ++b) {
-        if (hipHostMalloc((void**)&pin[b], chunk_cols * colb, hipHostMallocDefault) != hipSuccess) {
-            for (int k = 0; k < b; ++k) (void)hipHostFree(pin[k]);
-            ::close(fd);
-            return fail(VAMPOMI_ERR_OOM, "pinned staging buffer");
-        }
-        (void)hipEventCreate(&done[b]);
-    }
-    void* stage = nullptr;  // put_cols' device staging buffer (conversions only)
-    size_t stage_cap = 0;
-    vampomi_status st = VAMPOMI_OK;
-    int64_t i0 = 0;
-    int b = 0;
-    while (i0 < c->M && st == VAMPOMI_OK) {
-        const int64_t nc = std::min<int64_t>((int64_t)chunk_cols, c->M - i0);
-        if (used[b]) (void)hipEventSynchronize(done[b]);
-        const size_t want = (size_t)nc * colb;
-        const off_t off = (off_t)(c->S + i0) * (off_t)colb;
-        if (!pread_parallel(fd, pin[b], want, off, nt)) {
-            st = fail(VAMPOMI_ERR_IO, std::string("short read from methylation file ") + path);
-            break;
-        }
-        st = put_cols(c, i0, nc, pin[b], rows_in(c), in_es, &stage, &stage_cap);
-        if (st != VAMPOMI_OK) break;
-        if (hipEventRecord(done[b], c->st) != hipSuccess) {
-            st = fail(VAMPOMI_ERR_HIP, "host-to-device copy of the methylation shard");
-            break;
-        }
-        used[b] = true;
-        i0 += nc;
-        b = (b + 1) % NB;
-    }
-    (void)hipStreamSynchronize(c->st);
-    for (int k = 0; k < NB; ++k) {
-        (void)hipHostFree(pin[k]);
-        (void)hipEventDestroy(done[k]);
-    }
-    if (stage) (void)hipFree(stage);
-    ::close(fd);
-    if (st != VAMPOMI_OK) return st;
-    STCHK(na_end(c, look));
-    STCHK(quant_end(c));
-    STCHK(adjust_end(c));
-    return finish_X(c);
-}
-
-extern "C" vampomi_status vampomi_load_meth_file(vampomi_ctx* c, const char* path) { return load_file(c, path, 8); }
-
-extern "C" vampomi_status vampomi_load_meth_file_f32(vampomi_ctx* c, const char* path) {
-    return load_file(c, path, 4);
-}
-
-extern "C" vampomi_status vampomi_load_meth_file_u16(vampomi_ctx* c, const char* path) {
-    return load_file(c, path, 2);
-}
-
-extern "C" vampomi_status vampomi_generate_meth(vampomi_ctx* c, uint64_t seed, int kind) {
-    if (!c || (kind != VAMPOMI_GEN_GAUSS && kind != VAMPOMI_GEN_METH)) return fail(VAMPOMI_ERR_ARG, "bad argument");
-    if (c->N_file) return fail(VAMPOMI_ERR_STATE, "a context with a row subset loads its shard from a file or the host");
-    if (c->adj_R)
-        return fail(VAMPOMI_ERR_STATE, "a covariate-adjusted context loads its shard from a file or the host");
-    if (c->u16() && kind == VAMPOMI_GEN_GAUSS)
-        return fail(VAMPOMI_ERR_RANGE, "VAMPOMI_GEN_GAUSS values are not in [0, 1]: they cannot be stored as 16-bit "
-                                       "fixed point (VAMPOMI_STORE_U16)");
-    HIPCHK(hipSetDevice(c->device));
-    STCHK(ensure_X(c));
-    STCHK(quant_begin(c));
-    STCHK(na_begin(c, false));
-    STCHK(adjust_begin(c));  // (no adjustment here: the last load's record is forgotten)
-    if (!c->u16()) {
-        HIPCHK(vk::gen_markers(seed, kind, c->N, c->ld, c->S, c->M, c->X, c->ek(), c->st));
-        return finish_X(c);
-    }
-    // U16: the generator's doubles in chunks of columns (about 256 MB), each
-    // quantised into the shard as an ingest of the fp64 matrix would be
-    const int64_t chunk = std::min<int64_t>(std::max<int64_t>(c->M, 1),
-                                            std::max<int64_t>(1, io_chunk_bytes() / (c->ld * 8)));
-    void* stage = nullptr;
-    if (hipMalloc(&stage, (size_t)chunk * (size_t)c->ld * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(VAMPOMI_ERR_OOM, "device staging buffer of the generator");
-    }
-    hipError_t e = hipSuccess;
-    for (int64_t i0 = 0; i0 < c->M && e == hipSuccess; i0 += chunk) {
-        const int64_t nc = std::min(chunk, c->M - i0);
-        e = vk::gen_markers(seed, kind, c->N, c->ld, c->S + i0, nc, stage, vk::kXF64, c->st);
-        if (e == hipSuccess)
-            e = vk::quantise_cols((const double*)stage, c->ld, c->N, nc, (uint16_t*)c->X + i0 * c->ld, c->ld,
-                                  c->S + i0, c->qrec, c->st);
-    }
-    (void)hipStreamSynchronize(c->st);
-    (void)hipFree(stage);
-    if (e != hipSuccess) return fail(VAMPOMI_ERR_HIP, std::string("generate_meth: ") + hipGetErrorString(e));
-    STCHK(quant_end(c));
-    return finish_X(c);
-}
-
 static vampomi_status upload_phen(vampomi_ctx* c) {
     HIPCHK(hipMemcpyAsync(c->y, c->y_host.data(), (size_t)c->N * 8, hipMemcpyHostToDevice, c->st));
     STCHK(sync_stream(c, c->st));
@@ -2125,40 +1424,6 @@ extern "C" vampomi_status vampomi_get_marker_stats(vampomi_ctx* c, double* mave,
     if (msig && c->M > 0) HIPCHK(hipMemcpyAsync(msig, c->msig, (size_t)c->M * 8, hipMemcpyDeviceToHost, c->st));
     STCHK(sync_stream(c, c->st));
     return VAMPOMI_OK;
-}
-
-extern "C" vampomi_status vampomi_read_markers(vampomi_ctx* c, int64_t i0, int64_t count, double* out) {
-    if (!c || !out || i0 < 0 || count < 0 || i0 + count > c->M) return fail(VAMPOMI_ERR_ARG, "bad marker range");
-    if (!c->have_X) return fail(VAMPOMI_ERR_STATE, "no methylation data loaded");
-    HIPCHK(hipSetDevice(c->device));
-    const bool narrow = c->f32() || c->u16();
-    if (count > 0 && !narrow)
-        HIPCHK(hipMemcpy2DAsync(out, (size_t)c->N * 8, (const double*)c->X + i0 * c->ld, (size_t)c->ld * 8,
-                                (size_t)c->N * 8, (size_t)count, hipMemcpyDeviceToHost, c->st));
-    // fp32 / 16-bit storage: the stored values widened on the device (exact),
-    // in chunks of about 64 MB through a staging buffer
-    void* stage = nullptr;
-    if (count > 0 && narrow) {
-        const int64_t chunk = std::min<int64_t>(count, std::max<int64_t>(1, ((int64_t)64 << 20) / (c->N * 8)));
-        HIPCHK(hipMalloc(&stage, (size_t)chunk * (size_t)c->N * 8));
-        for (int64_t k = 0; k < count; k += chunk) {
-            const int64_t nc = std::min(chunk, count - k);
-            hipError_t e = c->u16() ? vk::dequant_cols((const uint16_t*)c->X + (i0 + k) * c->ld, c->ld, c->N, nc,
-                                                       (double*)stage, c->N, c->st)
-                                    : vk::widen_cols((const float*)c->X + (i0 + k) * c->ld, c->ld, c->N, nc,
-                                                     (double*)stage, c->N, c->st);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(out + k * c->N, stage, (size_t)nc * (size_t)c->N * 8, hipMemcpyDeviceToHost, c->st);
-            if (e != hipSuccess) {
-                (void)hipStreamSynchronize(c->st);
-                (void)hipFree(stage);
-                return fail(VAMPOMI_ERR_HIP, std::string("read_markers: ") + hipGetErrorString(e));
-            }
-        }
-    }
-    const vampomi_status st = sync_stream(c, c->st);
-    if (stage) (void)hipFree(stage);
-    return st;
 }
 
 extern "C" vampomi_status vampomi_simulate_phen(vampomi_ctx* c, uint64_t seed, double lam, double h2, double* beta_out) {

@@ -1,5 +1,5 @@
 // kdev.h — device helpers shared by the gfx950 kernel files (kernels.hip,
-// atax_team.hip).  Internal to libvampomi.
+// atax_team.hip, ingest.hip).  Internal to libvampomi.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +8,9 @@
 #include "kernels.h"
 
 namespace vk {
+
+constexpr int kBlock = 256;  // 4 waves of 64
+inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 typedef double v2d __attribute__((ext_vector_type(2)));
 typedef float v2f __attribute__((ext_vector_type(2)));

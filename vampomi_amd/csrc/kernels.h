@@ -286,52 +286,40 @@ hipError_t marker_stats(const Shard& s, double nonas, double alpha_scale, double
 // ---- synthetic data --------------------------------------------------------
 // (ek kXF32: X holds floats and receives the generator's value rounded to
 // nearest even; kXU16 is not generated in place: the engine quantises staged
-// fp64 chunks, quantise_cols)
+// fp64 chunks, convert_cols)
 hipError_t gen_markers(uint64_t seed, int kind, int64_t N, int64_t ld, int64_t S, int64_t M, void* X, int ek,
                        hipStream_t st);
-// ---- fp32 storage: conversions between a staged fp64 chunk and the shard -------
-// dst[c*ldd + j] = (float)src[c*lds + j] (nearest even), j < N, c < ncols
-hipError_t narrow_cols(const double* src, int64_t lds, int64_t N, int64_t ncols, float* dst, int64_t ldd,
-                       hipStream_t st);
-// dst[c*ldd + j] = (double)src[c*lds + j] (exact)
-hipError_t widen_cols(const float* src, int64_t lds, int64_t N, int64_t ncols, double* dst, int64_t ldd,
-                      hipStream_t st);
-// ---- 16-bit fixed-point storage (uint16_t k, value k * 2^-16) ----------------
-// What quantise_cols has seen since the record was zeroed (device memory, 4
-// words): every field is an integer sum, a minimum or a maximum, so none
-// depends on the order the launches' threads ran in.
+// ---- ingest and read-back (ingest.hip): the element conversions ---------------
+// What convert_cols and na_ingest_cols have seen of the entries they quantised
+// since the record was zeroed (device memory, 4 words): every field is an
+// integer sum, a minimum or a maximum, so none depends on the order the
+// launches' threads ran in.
 struct QuantRec {
     unsigned long long rejected;  // entries that are NaN, infinite, < 0 or > 1
-    unsigned long long first;     // the smallest index (col0 + c) * N + j of a rejected entry (~0: none)
+    unsigned long long first;     // the smallest index (col0 + c) * nfile + row of a rejected entry (~0: none)
     unsigned long long clamped;   // accepted entries that rounded to 65536 and were stored as 65535
     unsigned long long max_err;   // max |k * 2^-16 - x| over the accepted entries, as the bits of that double
 };
-// dst[c*ldd + j] = min(65535, rint(src[c*lds + j] * 65536)) (ties to even; the
-// product is exact), j < N, c < ncols, for 0 <= x <= 1 (-0.0 is 0); any other
-// entry stores 0 and is counted in *rec.  XS: double or float (widened first).
-// col0: the index of column 0, for rec->first
-hipError_t quantise_cols(const double* src, int64_t lds, int64_t N, int64_t ncols, uint16_t* dst, int64_t ldd,
-                         int64_t col0, QuantRec* rec, hipStream_t st);
-hipError_t quantise_cols(const float* src, int64_t lds, int64_t N, int64_t ncols, uint16_t* dst, int64_t ldd,
-                         int64_t col0, QuantRec* rec, hipStream_t st);
-// dst[c*ldd + j] = src[c*lds + j] * 2^-16 (exact, as a double and as a float)
-hipError_t dequant_cols(const uint16_t* src, int64_t lds, int64_t N, int64_t ncols, double* dst, int64_t ldd,
+// dst[c*ldd + j] = conv(src[c*lds + row(j)]), j < n, c < ncols: a chunk of
+// columns of nfile elements (lds >= nfile; a staged chunk's are packed, so a
+// column is only as aligned as its element) into columns of stride ldd.
+// rows == nullptr: n == nfile and row(j) = j; else row(j) = rows[j], n
+// ascending device indices in [0, nfile) (a row subset), and the stored bits
+// are those of the conversion of the chunk with the other rows taken out
+// beforehand.  src_ek / dst_ek (kXF64 / kXF32 / kXU16; a 16-bit element is a
+// uint16_t k, value k * 2^-16) pick conv:
+//   double -> float            nearest even
+//   float -> double            exact
+//   16 bits -> double, float   k * 2^-16, exact
+//   double, float -> 16 bits   min(65535, rint(x * 65536)) (ties to even; the
+//       product is exact; a float is widened first) for 0 <= x <= 1 (-0.0 is
+//       0); any other entry stores 0 and is counted in *rec, its index
+//       (col0 + c) * nfile + row(j) (col0: the index of column 0)
+//   the kinds agree            a copy
+// rec is not read for the other conversions
+hipError_t convert_cols(const void* src, int src_ek, int64_t lds, const int32_t* rows, int64_t n, int64_t ncols,
+                        void* dst, int dst_ek, int64_t ldd, int64_t nfile, int64_t col0, QuantRec* rec,
                         hipStream_t st);
-hipError_t dequant_cols(const uint16_t* src, int64_t lds, int64_t N, int64_t ncols, float* dst, int64_t ldd,
-                        hipStream_t st);
-// ---- row subset: the conversions above with a row gather ------------------------
-// dst[c*ldd + j] = conv(src[c*lds + rows[j]]), j < n, c < ncols, for a staged
-// chunk of packed columns of nfile elements (lds >= nfile; a column is only as
-// aligned as its element) and n ascending device indices rows[j] in
-// [0, nfile).  src_ek / dst_ek (kXF64 / kXF32 / kXU16) pick conv: exactly what
-// narrow_cols, widen_cols, dequant_cols and quantise_cols store, and a copy
-// where the kinds agree, so the stored bits are those of the conversion of the
-// chunk with the other rows taken out beforehand.  Into kXU16 from doubles or
-// floats, *rec takes the kept entries only, its first as
-// (col0 + c) * nfile + rows[j] (the file's row); rec is not read otherwise
-hipError_t gather_cols(const void* src, int src_ek, int64_t lds, const int32_t* rows, int64_t n, int64_t ncols,
-                       void* dst, int dst_ek, int64_t ldd, int64_t nfile, int64_t col0, QuantRec* rec,
-                       hipStream_t st);
 // ---- missing values (NaN): the column-wise ingest ----------------------------
 // What na_ingest_cols has seen since the record was zeroed (first: all ones):
 // integer sums and a minimum, so none depends on the order anything ran in.
@@ -342,11 +330,9 @@ struct NaRec {
     unsigned long long masked;   // columns stored as zeros (kNaMean)
 };
 enum { kNaFatal = 1, kNaMean = 2 };  // (VAMPOMI_NA_FATAL / VAMPOMI_NA_MEAN)
-// The ingest conversions (narrow_cols, widen_cols, quantise_cols, gather_cols;
-// a copy where the kinds agree) of a staged chunk of doubles or floats
-// (src_ek kXF64 / kXF32) with a NaN policy.  rows == nullptr: the n = nfile
-// rows of a column as they are; else the n ascending device indices of the
-// kept rows, as gather_cols takes them.  One workgroup per column, two sweeps:
+// convert_cols' conversions of a staged chunk of doubles or floats (src_ek
+// kXF64 / kXF32) with a NaN policy; rows, n and nfile as convert_cols takes
+// them.  One workgroup per column, two sweeps:
 //   1. the NaNs among the kept rows are counted (cnt[c], and *nrec) and the
 //      other kept entries summed in fp64: thread t adds rows t, t + 256, ...
 //      in that order, each wave's 64 sums are folded by wave_sum's butterfly,
@@ -355,7 +341,7 @@ enum { kNaFatal = 1, kNaMean = 2 };  // (VAMPOMI_NA_FATAL / VAMPOMI_NA_MEAN)
 //   2. kNaMean: each kept entry is stored as conv(x), a NaN as conv(s / n_obs);
 //      a column with n_obs == 0 or (double)n_missing > max_frac * (double)n is
 //      stored as zeros.  Into kXU16 the observed entries (a masked column's
-//      too) go through *qrec as in quantise_cols; the fill and the zeros do not.
+//      too) go through *qrec as in convert_cols; the fill and the zeros do not.
 //      kNaFatal: the same for a column without NaN; a column with one is not
 //      stored (the load fails).
 // cnt: ncols device counters (the chunk's slice of the shard's)
@@ -363,13 +349,13 @@ hipError_t na_ingest_cols(const void* src, int src_ek, int64_t lds, const int32_
                           void* dst, int dst_ek, int64_t ldd, int64_t nfile, int64_t col0, int mode, double max_frac,
                           int64_t* cnt, NaRec* nrec, QuantRec* qrec, hipStream_t st);
 // ---- covariate adjustment: the residual of each column on an orthonormal basis ---
-// src: an fp64 work block of ncols packed columns of n rows (what the ingest
-// conversions above leave with dst_ek = kXF64, ldd = n); Q: n x R doubles on
+// src: an fp64 work block of ncols packed columns of n rows (what convert_cols
+// or na_ingest_cols leaves with dst_ek = kXF64, ldd = n); Q: n x R doubles on
 // the device, column-major and packed, orthonormal (R <= kAdjMaxR).  Per column
 // c = Q^T x, r = x - Q c in fp64, stored as dst[col*ldd + j] = (XD)r_j (dst_ek
 // kXF64 or kXF32: one rounding); a column with ||r||^2 <= 1e-20 ||x||^2 is
 // stored as zeros, flags[col] = 1 (else 0) and *absorbed is incremented.  The
-// sums run in an order that depends on n and R alone (kernels.hip), so a
+// sums run in an order that depends on n and R alone (ingest.hip), so a
 // column's stored bits depend on neither the chunk nor the columns beside it.
 constexpr int kAdjMaxR = 65;  // VAMPOMI_MAX_C + 1: the intercept and every covariate
 hipError_t adjust_cols(const double* src, int64_t n, int64_t ncols, const double* Q, int R, void* dst, int dst_ek,
