@@ -1,4 +1,4 @@
-// ctx.h — libvampomi internals shared by engine.cpp, ingest.cpp, pcg.cpp and vamp.cpp.
+// ctx.h — libvampomi internals shared by engine.cpp, ingest.cpp, assoc.cpp, pcg.cpp and vamp.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -253,6 +253,14 @@ void resolve_timing(vampomi_ctx* c);
 // counts a launch of class cls with K right-hand sides (bytes, flops: its
 // algorithmic work); returns HIP events for it if it is sampled (else nulls)
 TimedLaunch launch_stat(vampomi_ctx* c, int cls, int K, double bytes, double flops);
+// algorithmic bytes / flops of one pass over the shard with K right-hand sides
+double pass_bytes(const vampomi_ctx* c, int K);
+double pass_flops(const vampomi_ctx* c, int K);
+// n doubles of a caller's vector (mem: VAMPOMI_MEM_HOST / _DEVICE) into a
+// device buffer on the context's stream; stage_out: back, then the stream is
+// synchronised (the caller may read dst)
+vampomi_status stage_in(vampomi_ctx* c, const double* src, int64_t n, int mem, double* dst);
+vampomi_status stage_out(vampomi_ctx* c, const double* src, int64_t n, int mem, double* dst);
 // forgets the counts since `before` and the samples queued since pending_mark
 // (the gated launches of a CG step queued after the solve had stopped)
 void drop_launches(vampomi_ctx* c, size_t pending_mark, const vampomi_stats& before);

@@ -77,11 +77,11 @@ static hipEvent_t ev_get(vampomi_ctx* c) {
 // algorithmic bytes / flops of one pass with K right-hand sides:
 // X once (at its stored element size), the K N-vectors, mave/msig and the K
 // M-vectors; (x - mu) once per element and one fma per right-hand side.
-static double pass_bytes(const vampomi_ctx* c, int K) {
+double pass_bytes(const vampomi_ctx* c, int K) {
     return (double)c->esize() * (double)c->N * (double)c->M + 8.0 * K * (double)c->N +
            8.0 * (2.0 + K) * (double)c->M;
 }
-static double pass_flops(const vampomi_ctx* c, int K) { return (double)c->N * (double)c->M * (1.0 + 2.0 * K); }
+double pass_flops(const vampomi_ctx* c, int K) { return (double)c->N * (double)c->M * (1.0 + 2.0 * K); }
 
 static vampomi_kernel_stat* stat_of(vampomi_ctx* c, int cls) {
     return cls == 0 ? &c->stats.ax : cls == 1 ? &c->stats.atx : cls == 3 ? &c->stats.op : cls == 4 ? &c->stats.coll
@@ -1465,14 +1465,14 @@ extern "C" vampomi_status vampomi_simulate_phen_binary(vampomi_ctx* c, uint64_t 
 // ---------------------------------------------------------------------------
 // operator entry points
 // ---------------------------------------------------------------------------
-static vampomi_status stage_in(vampomi_ctx* c, const double* src, int64_t n, int mem, double* dst) {
+vampomi_status stage_in(vampomi_ctx* c, const double* src, int64_t n, int mem, double* dst) {
     if (n <= 0) return VAMPOMI_OK;
     HIPCHK(hipMemcpyAsync(dst, src, (size_t)n * 8, mem == VAMPOMI_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                           c->st));
     return VAMPOMI_OK;
 }
 
-static vampomi_status stage_out(vampomi_ctx* c, const double* src, int64_t n, int mem, double* dst) {
+vampomi_status stage_out(vampomi_ctx* c, const double* src, int64_t n, int mem, double* dst) {
     if (n > 0)
         HIPCHK(hipMemcpyAsync(dst, src, (size_t)n * 8, mem == VAMPOMI_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
                               c->st));
@@ -1648,257 +1648,6 @@ extern "C" vampomi_status vampomi_denoise_bin(vampomi_ctx* c, const double* p1, 
     return vampomi_denoise_bin_cov(c, p1, tau1, nullptr, z1, sum_d, mem);
 }
 
-// --run-mode association_test --pval-method loo (src/main_meth.cpp:245-264,
-// data::pvals_loo src/data.cpp:385-417).  COLLECTIVE (one A.x).
-extern "C" vampomi_status vampomi_assoc_loo(vampomi_ctx* c, const double* est, double* pvals, double* stats,
-                                            int mem) {
-    CollScope cs_(c);
-    if (!c || (!est && c->M > 0)) return fail(VAMPOMI_ERR_ARG, "null argument");
-    if (!c->have_X || !c->have_y) return fail(VAMPOMI_ERR_STATE, "load methylation data and phenotype first");
-    HIPCHK(hipSetDevice(c->device));
-    const int64_t M = c->M, N = c->N, Mx = std::max<int64_t>(M, 1), ld = c->ld;
-    double* e = c->mbuf;            // estimate-file values
-    double* x1 = c->mbuf + Mx;      // x1_hat * sqrt(N)
-    double* pv = c->mbuf + 2 * Mx;  // p-values
-    double* st = c->mbuf + 3 * Mx;  // 5 sums per marker (slots 3..7)
-    double* z1 = c->nbuf;
-    double* ymod = c->nbuf + ld;
-    STCHK(stage_in(c, est, M, mem, e));
-    HIPCHK(vk::mul_scalar(M, e, std::sqrt((double)N), x1, c->st));  // :254-255
-    const double* xs[1] = {x1};
-    STCHK(ax_dev(c, 1, xs, z1));                                     // :257
-    HIPCHK(vk::axpby(N, 1.0, c->y, -1.0, z1, ymod, c->st));          // y_mod = y - z1 (data.cpp:390-391)
-    if (ld > N) HIPCHK(hipMemsetAsync(ymod + N, 0, (size_t)(ld - N) * 8, c->st));
-    // raw X once, ymod, x1, the five sums; per element 1 div, 2 mul + 1 add
-    // for ym, 5 accumulations (3 of them products)
-    TimedLaunch t = launch_stat(c, 2, 1,
-                                (double)c->esize() * (double)N * (double)M + 8.0 * (double)N + 8.0 * 6.0 * (double)M,
-                                11.0 * (double)N * (double)M);
-    HIPCHK(vk::loo_sums(c->shard(), ymod, x1, std::sqrt((double)N), st, c->st, c->loo_variant, vk::Timing{t.a, t.b}));  // :393-416
-    c->stats.a_passes_exec++;
-    HIPCHK(vk::loo_pvals(M, st, (int)N, pv, c->st));
-    if (stats) STCHK(stage_out(c, st, 5 * M, mem, stats));
-    if (pvals) STCHK(stage_out(c, pv, M, mem, pvals));
-    STCHK(sync_stream(c, c->st));
-    if (c->timing) resolve_timing(c);
-    return VAMPOMI_OK;
-}
-
-// vampomi_assoc_loo for T phenotypes with the shard read once per chunk of up
-// to vk::kLooMultiMax of them: per chunk one batched A.x
-// (none with est == NULL), ymod_t = y_t - z_t, one vk::loo_multi_sums (a chunk
-// of one: vk::loo_sums), the p-values of the chunk's blocks.  Block t is bit
-// for bit vampomi_set_phen(Y_t) + vampomi_assoc_loo(est_t) under the default
-// association variant.  COLLECTIVE (one A.x per chunk; est is NULL on every
-// rank or on none).
-extern "C" vampomi_status vampomi_assoc_loo_multi(vampomi_ctx* c, int T, const double* Y, int64_t ldY,
-                                                  int standardize, const double* est, double* pvals, double* stats,
-                                                  int mem) {
-    CollScope cs_(c);
-    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
-    if (T < 1) return fail(VAMPOMI_ERR_ARG, "assoc_loo_multi: T < 1");
-    if (!Y) return fail(VAMPOMI_ERR_ARG, "assoc_loo_multi: null Y");
-    if (ldY < c->N) return fail(VAMPOMI_ERR_ARG, "assoc_loo_multi: ldY < N");
-    if (!c->have_X) return fail(VAMPOMI_ERR_STATE, "load methylation data first");
-    HIPCHK(hipSetDevice(c->device));
-    const int64_t M = c->M, N = c->N, Mx = std::max<int64_t>(M, 1), ld = c->ld;
-    constexpr int KM = vk::kLooMultiMax;
-    if (!c->am_n) {
-        STCHK(dev_alloc(&c->am_n, (size_t)2 * KM * ld));
-        HIPCHK(hipMemsetAsync(c->am_n, 0, (size_t)2 * KM * ld * 8, c->st));  // pad rows stay zero
-    }
-    if (!c->am_m) STCHK(dev_alloc(&c->am_m, (size_t)8 * KM * Mx));
-    double* yd = c->am_n;                  // y_t
-    double* ymod = c->am_n + KM * ld;      // y_t - z_t
-    double* e = c->am_m;                   // estimate-file values
-    double* x1 = c->am_m + KM * Mx;        // x1_hat * sqrt(N)
-    double* pv = c->am_m + 2 * KM * Mx;    // p-values
-    double* st = c->am_m + 3 * KM * Mx;    // KT blocks of 5 sums per marker
-    double* z = c->nbuf;                   // A x1_t
-    // every column as vampomi_set_phen prepares it (host; the context's own
-    // phenotype is not touched)
-    std::vector<double> yh((size_t)T * (size_t)N), col;
-    for (int t = 0; t < T; ++t) {
-        col.assign(Y + (int64_t)t * ldY, Y + (int64_t)t * ldY + N);
-        adjust_phen(c, col);
-        if (standardize) vio::standardize_phen(col);
-        std::copy(col.begin(), col.end(), yh.begin() + (size_t)t * (size_t)N);
-    }
-    const double sqrtN = std::sqrt((double)N);
-    for (int t0 = 0; t0 < T; t0 += KM) {
-        const int KT = std::min(KM, T - t0);
-        double* ym = est ? ymod : yd;  // without estimates ymod_t = y_t
-        for (int k = 0; k < KT; ++k)
-            HIPCHK(hipMemcpyAsync(yd + (int64_t)k * ld, yh.data() + (size_t)(t0 + k) * (size_t)N, (size_t)N * 8,
-                                  hipMemcpyHostToDevice, c->st));
-        if (est) {
-            const double* xs[KM] = {};
-            for (int k = 0; k < KT; ++k) {
-                STCHK(stage_in(c, est + (int64_t)(t0 + k) * M, M, mem, e + k * Mx));
-                HIPCHK(vk::mul_scalar(M, e + k * Mx, sqrtN, x1 + k * Mx, c->st));
-                xs[k] = x1 + k * Mx;
-            }
-            STCHK(ax_dev(c, KT, xs, z));
-            for (int k = 0; k < KT; ++k)
-                HIPCHK(vk::axpby(N, 1.0, yd + (int64_t)k * ld, -1.0, z + (int64_t)k * ld, ymod + (int64_t)k * ld, c->st));
-        } else {
-            HIPCHK(hipMemsetAsync(x1, 0, (size_t)KT * Mx * 8, c->st));
-        }
-        if (KT == 1) {
-            TimedLaunch tl = launch_stat(c, 2, 1,
-                                         (double)c->esize() * (double)N * (double)M + 8.0 * (double)N + 8.0 * 6.0 * (double)M,
-                                         11.0 * (double)N * (double)M);
-            HIPCHK(vk::loo_sums(c->shard(), ym, x1, sqrtN, st, c->st, c->loo_variant, vk::Timing{tl.a, tl.b}));
-        } else {
-            // raw X once, KT ymod and x1 vectors, KT blocks of sums; per element
-            // 4 operations for the quotient and the x-only sums, 7 per phenotype.
-            // (Every width is booked into the one stats.loo record, which has
-            // no per-K records: its time is exact at timing period 1 only.  At
-            // a longer period it is the sampled mean times the launch count
-            // over launches of different widths and costs, so it is biased)
-            TimedLaunch tl = launch_stat(c, 2, KT,
-                                         (double)c->esize() * (double)N * (double)M + 8.0 * (double)N * KT +
-                                             8.0 * 6.0 * (double)M * KT,
-                                         (4.0 + 7.0 * KT) * (double)N * (double)M);
-            HIPCHK(vk::loo_multi_sums(c->shard(), KT, ym, x1, sqrtN, st, c->st, vk::Timing{tl.a, tl.b}));
-        }
-        c->stats.a_passes_exec++;
-        HIPCHK(vk::loo_pvals((int64_t)KT * M, st, (int)N, pv, c->st));
-        if (stats) STCHK(stage_out(c, st, 5 * M * KT, mem, stats + (int64_t)t0 * 5 * M));
-        if (pvals) STCHK(stage_out(c, pv, M * KT, mem, pvals + (int64_t)t0 * M));
-    }
-    STCHK(sync_stream(c, c->st));
-    if (c->timing) resolve_timing(c);
-    return VAMPOMI_OK;
-}
-
-// The leave-one-chromosome-out test: the segmented A.x over
-// the markers sorted by (label, index), z and y_c, the marker pass against the
-// phenotype of each marker's label.  COLLECTIVE (one all-reduce of G ld-vectors;
-// none with est == NULL, which is NULL on every rank or on none).
-extern "C" vampomi_status vampomi_assoc_loco(vampomi_ctx* c, const double* est, const int32_t* labels, int G,
-                                             double* pvals, double* stats, double* resid, int mem) {
-    CollScope cs_(c);
-    if (!c) return fail(VAMPOMI_ERR_ARG, "null context");
-    if (!labels && c->M > 0) return fail(VAMPOMI_ERR_ARG, "assoc_loco: null labels");
-    if (G < 1 || G > vk::kSegMax)
-        return fail(VAMPOMI_ERR_ARG, "assoc_loco: G = " + std::to_string(G) + " outside [1, " +
-                                         std::to_string(vk::kSegMax) + "]");
-    for (int64_t i = 0; i < c->M; ++i)
-        if (labels[i] < 0 || labels[i] >= G)
-            return fail(VAMPOMI_ERR_ARG, "assoc_loco: label " + std::to_string(labels[i]) + " of marker " +
-                                             std::to_string(i) + " outside [0, " + std::to_string(G) + ")");
-    if (!c->have_X || !c->have_y) return fail(VAMPOMI_ERR_STATE, "load methylation data and phenotype first");
-    HIPCHK(hipSetDevice(c->device));
-    const int64_t M = c->M, N = c->N, Mx = std::max<int64_t>(M, 1), ld = c->ld;
-    vk::SegLists L;
-    vk::seg_lists(labels, M, G, &L);
-    const int nchunks = L.nchunks(), ngroups = L.ngroups();
-    // the lists in one device block: cols, chunk_at, lab_chunk, grp_col, grp_lab
-    const int64_t o_chunk = M, o_lab = o_chunk + nchunks + 1, o_gcol = o_lab + G + 1,
-                  o_glab = o_gcol + (int64_t)ngroups * vk::kLocoG, words = o_glab + ngroups;
-    if (words > c->lc_idx_cap) {
-        if (c->lc_idx) (void)hipFree(c->lc_idx);
-        c->lc_idx = nullptr;
-        c->lc_idx_cap = 0;
-        // (what any labelling of this shard needs, so a later call does not grow it)
-        const int64_t cap = M + vk::seg_max_chunks(M) + 1 + vk::kSegMax + 1 + vk::seg_max_groups(M) * (vk::kLocoG + 1);
-        hipError_t e = hipMalloc((void**)&c->lc_idx, (size_t)cap * sizeof(int32_t));
-        if (e != hipSuccess) return fail(VAMPOMI_ERR_OOM, std::string("hipMalloc(label lists): ") + hipGetErrorString(e));
-        c->lc_idx_cap = cap;
-    }
-    std::vector<int32_t> host((size_t)words);
-    std::copy(L.cols.begin(), L.cols.end(), host.begin());
-    std::copy(L.chunk_at.begin(), L.chunk_at.end(), host.begin() + o_chunk);
-    std::copy(L.lab_chunk.begin(), L.lab_chunk.end(), host.begin() + o_lab);
-    std::copy(L.grp_col.begin(), L.grp_col.end(), host.begin() + o_gcol);
-    std::copy(L.grp_lab.begin(), L.grp_lab.end(), host.begin() + o_glab);
-    HIPCHK(hipMemcpyAsync(c->lc_idx, host.data(), (size_t)words * sizeof(int32_t), hipMemcpyHostToDevice, c->st));
-    STCHK(sync_stream(c, c->st));  // host is a local: the copy has left it
-    double* pv = c->mbuf + 2 * Mx;  // p-values
-    double* st = c->mbuf + 3 * Mx;  // 5 sums per marker
-    const double* ys = c->y;        // est == NULL: every y_c is y
-    int64_t ldy = 0;
-    if (est) {
-        if (G > c->lc_G) {
-            dev_free(c->lc_z);
-            c->lc_G = 0;
-            STCHK(dev_alloc(&c->lc_z, (size_t)G * ld));
-            HIPCHK(hipMemsetAsync(c->lc_z, 0, (size_t)G * ld * 8, c->st));  // pad rows stay zero
-            c->lc_G = G;
-        }
-        if (nchunks > c->lc_slots) {
-            dev_free(c->lc_part);
-            c->lc_slots = 0;
-            STCHK(dev_alloc(&c->lc_part, (size_t)nchunks * ld));
-            c->lc_slots = nchunks;
-        }
-        double* e = c->mbuf;        // estimate-file values
-        double* x1 = c->mbuf + Mx;  // x1_hat * sqrt(N)
-        STCHK(stage_in(c, est, M, mem, e));
-        HIPCHK(vk::mul_scalar(M, e, std::sqrt((double)N), x1, c->st));
-        // X once, the lists and x1, one slot per chunk written and read back
-        TimedLaunch t = launch_stat(c, 0, 1, pass_bytes(c, 1) + 16.0 * (double)N * nchunks, pass_flops(c, 1));
-        HIPCHK(vk::ax_seg_partial(c->shard(), x1, c->lc_idx, c->lc_idx + o_chunk, nchunks, c->lc_part, c->st,
-                                  vk::Timing{t.a, t.b}));
-        c->stats.a_passes_exec++;
-        if (!c->use_comm) {
-            HIPCHK(vk::ax_seg_reduce(G, N, ld, c->lc_idx + o_lab, c->lc_part, c->lc_z, c->sqrtN, c->st));
-            HIPCHK(vk::loco_resid(G, N, ld, c->y, c->lc_z, 0.0, c->st));
-        } else {
-            HIPCHK(vk::ax_seg_reduce(G, N, ld, c->lc_idx + o_lab, c->lc_part, c->lc_z, 0.0, c->st));
-            STCHK(allreduce_dev(c, c->lc_z, (size_t)G * ld));  // ONE all-reduce for all G vectors
-            HIPCHK(vk::loco_resid(G, N, ld, c->y, c->lc_z, c->sqrtN, c->st));
-        }
-        ys = c->lc_z;
-        ldy = ld;
-    }
-    // raw X once, G phenotypes, the lists, five sums per marker; per element 5
-    // accumulations (3 of them products) less the two shared ones of a group
-    TimedLaunch t = launch_stat(c, 2, 1,
-                                (double)c->esize() * (double)N * (double)M + 8.0 * (double)N * (est ? G : 1) +
-                                    8.0 * 6.0 * (double)M,
-                                7.0 * (double)N * (double)M);
-    HIPCHK(vk::loco_sums(c->shard(), ys, ldy, c->lc_idx + o_gcol, c->lc_idx + o_glab, ngroups, st, c->st,
-                         vk::Timing{t.a, t.b}));
-    c->stats.a_passes_exec++;
-    HIPCHK(vk::loo_pvals(M, st, (int)N, pv, c->st));
-    if (resid)
-        for (int g = 0; g < G; ++g)
-            HIPCHK(hipMemcpyAsync(resid + (int64_t)g * N, ys + (int64_t)g * ldy, (size_t)N * 8, hipMemcpyDeviceToHost,
-                                  c->st));
-    if (stats) STCHK(stage_out(c, st, 5 * M, mem, stats));
-    if (pvals) STCHK(stage_out(c, pv, M, mem, pvals));
-    STCHK(sync_stream(c, c->st));
-    if (c->timing) resolve_timing(c);
-    return VAMPOMI_OK;
-}
-
-extern "C" vampomi_status vampomi_read_labels(const char* path, int64_t Mt, int32_t* labels, int* G, char* names,
-                                              size_t names_cap) {
-    if (!path || Mt < 0) return fail(VAMPOMI_ERR_ARG, "read_labels: null path or Mt < 0");
-    std::vector<int32_t> lab;
-    std::vector<std::string> nm;
-    std::vector<int64_t> cnt;
-    std::string err;
-    switch (vio::read_labels(path, Mt, vk::kSegMax, lab, nm, cnt, &err)) {
-        case 0: break;
-        case -1: return fail(VAMPOMI_ERR_IO, err);
-        default: return fail(VAMPOMI_ERR_ARG, err);
-    }
-    if (labels) std::copy(lab.begin(), lab.end(), labels);
-    if (G) *G = (int)nm.size();
-    if (names) {
-        std::string all;
-        for (const std::string& s : nm) all += s + "\n";
-        if (all.size() + 1 > names_cap)
-            return fail(VAMPOMI_ERR_ARG, "read_labels: names_cap holds " + std::to_string(names_cap) + " bytes, " +
-                                             std::to_string(all.size() + 1) + " are needed");
-        std::memcpy(names, all.c_str(), all.size() + 1);
-    }
-    return VAMPOMI_OK;
-}
-
 // --run-mode test (src/main_meth.cpp:165-199): one estimate's R2 test and
 // squared correlation on the context's (test) data set.  COLLECTIVE (one A.x).
 extern "C" vampomi_status vampomi_test_metrics(vampomi_ctx* c, const double* est, double* r2, double* corr2,
@@ -1923,17 +1672,6 @@ extern "C" vampomi_status vampomi_test_metrics(vampomi_ctx* c, const double* est
     const double corr = s[3] / std::sqrt(s[4] * s[2]);                                     // :190
     if (corr2) *corr2 = corr * corr;
     if (c->timing) resolve_timing(c);
-    return VAMPOMI_OK;
-}
-
-// --pval-method se (src/main_meth.cpp:218-242): rank-local
-extern "C" vampomi_status vampomi_assoc_se(vampomi_ctx* c, const double* r1, double gam1, double* pvals, int mem) {
-    if (!c || (!r1 && c->M > 0) || (!pvals && c->M > 0)) return fail(VAMPOMI_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(c->device));
-    const int64_t Mx = std::max<int64_t>(c->M, 1);
-    STCHK(stage_in(c, r1, c->M, mem, c->mbuf));
-    HIPCHK(vk::se_pvals(c->M, c->mbuf, gam1, c->N, c->mbuf + Mx, c->st));
-    STCHK(stage_out(c, c->mbuf + Mx, c->M, mem, pvals));
     return VAMPOMI_OK;
 }
 

@@ -1,5 +1,5 @@
 // kdev.h — device helpers shared by the gfx950 kernel files (kernels.hip,
-// atax_team.hip, ingest.hip).  Internal to libvampomi.
+// atax_team.hip, ingest.hip, assoc.hip).  Internal to libvampomi.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -47,6 +47,8 @@ __device__ __forceinline__ xpair_t<E> ldx(const E* p) {
     if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const xpair_t<E>*>(p));
     return *reinterpret_cast<const xpair_t<E>*>(p);
 }
+// a row pair of an N-vector (16-byte aligned: ld-padded vectors, even rows)
+__device__ __forceinline__ v2d ld2(const double* p) { return *reinterpret_cast<const v2d*>(p); }
 __device__ __forceinline__ v2d widen(v2d x) { return x; }
 __device__ __forceinline__ v2d widen(v2f x) { return v2d{(double)x.x, (double)x.y}; }
 __device__ __forceinline__ v2d widen(v2h x) { return v2d{(double)x.x * 0x1p-16, (double)x.y * 0x1p-16}; }
