@@ -132,7 +132,7 @@ static double allreduce1(const orc_problem* pb, double v) {
 /*    in order; a block adds its 4 waves' xor-butterfly sums in wave order;    */
 /*    the last block's thread t adds the partials of blocks t, t + 256, ...,   */
 /*    then the same butterfly and wave order: dots_part / block_put_sums /     */
-/*    red_final in kernels.hip) with nblk = red_blocks(n) for the dots, the    */
+/*    red_final: vec.hip, kdev.h) with nblk = red_blocks(n) for the dots, the  */
 /*    CG's cg_init / cg_update sums and the denoisers' sums, ceil(M/256) for   */
 /*    the EM round's (em_kernel); the CG's <d,p> as the one-pass operator      */
 /*    forms it (each workgroup over the columns its team member owns, then    */
@@ -175,14 +175,14 @@ static double block256(const double* th) {
     return ((wave64(th) + wave64(th + 64)) + wave64(th + 128)) + wave64(th + 192);
 }
 
-static int dev_red_blocks(int64_t n) { /* kernels.hip red_blocks */
+static int dev_red_blocks(int64_t n) { /* vec.hip red_blocks */
     int64_t b = (n + 511) / 512;
     if (b < 1) b = 1;
     if (b > 1024) b = 1024;
     return (int)b;
 }
 
-static int dev_cg_blocks(int64_t M) { /* kernels.hip cg_update: mblocks (2 elements per thread) */
+static int dev_cg_blocks(int64_t M) { /* pcg.hip cg_update: mblocks (2 elements per thread) */
     int64_t b = (M + 511) / 512;
     if (b < 1) b = 1;
     if (b > 512) b = 512;

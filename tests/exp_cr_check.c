@@ -1,5 +1,5 @@
 /* CPU check behind the device exp of the probit denoiser
- * (vampomi_amd/csrc/exp_cr.h, used by erfcx_ref in kernels.hip; the
+ * (vampomi_amd/csrc/exp_cr.h, used by erfcx_ref in probit.hip; the
  * reference's erfcx calls glibc's exp, src/utilities.cpp:293-363).
  *
  * For n arguments in three ranges (erfcx's s = x^2 in [0, 100]; every

@@ -1,4 +1,4 @@
-/* CPU check of the association pass's division (vampomi_amd/csrc/kernels.hip
+/* CPU check of the association pass's division (vampomi_amd/csrc/assoc.hip
  * loo_kernel, FASTDIV): q = fma(fma(-x*r, d, x), r, x*r) with r = RN(1/d)
  * equals the IEEE quotient x / d.  Prints the number of mismatches. */
 #include <math.h>

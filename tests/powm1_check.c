@@ -1,4 +1,4 @@
-/* CPU check behind the device CG step (vampomi_amd/csrc/kernels.hip
+/* CPU check behind the device CG step (vampomi_amd/csrc/pcg.hip
  * cg_decide_kernel): the reference forms beta with pow(rz, -1)
  * (src/vamp.cpp:731); the device uses the correctly rounded 1.0 / rz.
  * glibc's pow is not correctly rounded: prints the number of mismatches, the

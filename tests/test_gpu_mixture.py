@@ -1,5 +1,5 @@
 """vampomi_denoise element by element (denoise_kernel, g1_g1d in
-kernels.hip), where the norm-relative checks of the runs see nothing: small
+vec.hip), where the norm-relative checks of the runs see nothing: small
 elements (spike-dominated markers, x1 ~ 1e-6 |r1|), gam1 from the run's first
 iterations (1e-6, where g1d cancels ~1e7-fold) to the |sigma| < 1e-10
 shortcut, r1 = +-0 and |r1| tens of standard deviations out, mixtures of 2 to

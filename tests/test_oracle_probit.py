@@ -129,7 +129,7 @@ def _block256(th):
 
 
 def _dev_red_py(a, b, nblk):
-    """kernels.hip's grouping of a reduction (dots_part, block_put_sums, red_final), in Python floats."""
+    """The device's grouping of a reduction (dots_part in vec.hip; block_put_sums, red_final in kdev.h), in Python floats."""
     n, stride = len(a), nblk * 256
     part = []
     for bk in range(nblk):
@@ -152,7 +152,7 @@ def _dev_red_py(a, b, nblk):
 def test_association_modes():
     """The oracle's association modes (vamp_oracle.c, the probit bar's
     measurement): the default is orc_dot; DEVICE groups a sum exactly as
-    kernels.hip's reductions do (checked against a Python restatement of
+    vec.hip's reductions do (checked against a Python restatement of
     dots_part / block_put_sums / red_final, bit for bit) and <d,p> as the team
     operator does; REFRUN with one thread is the reference's sequential loop
     and with several a reordering of the same chunk sums."""

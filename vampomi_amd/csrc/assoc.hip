@@ -13,24 +13,7 @@
 #include <cstdlib>
 #include <string>
 
-#include <hip/hip_ext.h>
-
 namespace vk {
-
-// One launch for the three storages of X: k64, k32 and k16 are the same body
-// over double, float and 16-bit columns (the family's three __global__
-// wrappers); the one of the shard's element type gets (X, ld, args...), with
-// the timing events in its dispatch packet.
-template <class K64, class K32, class K16, class... A>
-static void launch_xe(const Shard& s, K64 k64, K32 k32, K16 k16, dim3 grid, dim3 block, hipStream_t st,
-                      const Timing& tm, A... args) {
-    if (s.u16)
-        hipExtLaunchKernelGGL(k16, grid, block, 0, st, tm.start, tm.stop, 0, s.x16(), s.ld, args...);
-    else if (s.f32)
-        hipExtLaunchKernelGGL(k32, grid, block, 0, st, tm.start, tm.stop, 0, s.x32(), s.ld, args...);
-    else
-        hipExtLaunchKernelGGL(k64, grid, block, 0, st, tm.start, tm.stop, 0, s.x64(), s.ld, args...);
-}
 
 // ---------------------------------------------------------------------------
 // association tests: data::pvals_loo (src/data.cpp:385-417) and the SE

@@ -1319,15 +1319,8 @@ bool ax_team_plan(int64_t N, int64_t M, int cus, AxPlan* out) {
 template <int S, int K, bool FU>
 static void launch_axt(const Shard& s, const AxPlan& pl, CPtrs x, double* part, hipStream_t st, const Timing& tm,
                        const AxFuse& fu) {
-    if (s.u16)
-        hipExtLaunchKernelGGL((ax_team_kernel_u16<S, K, FU>), dim3(pl.groups), dim3(kTmThreads), 0, st, tm.start,
-                              tm.stop, 0, s.x16(), s.ld, s.N, s.M, s.mave, s.msig, x, part, fu, pl.T, pl.TR);
-    else if (s.f32)
-        hipExtLaunchKernelGGL((ax_team_kernel_f32<S, K, FU>), dim3(pl.groups), dim3(kTmThreads), 0, st, tm.start,
-                              tm.stop, 0, s.x32(), s.ld, s.N, s.M, s.mave, s.msig, x, part, fu, pl.T, pl.TR);
-    else
-        hipExtLaunchKernelGGL((ax_team_kernel<S, K, FU>), dim3(pl.groups), dim3(kTmThreads), 0, st, tm.start,
-                              tm.stop, 0, s.x64(), s.ld, s.N, s.M, s.mave, s.msig, x, part, fu, pl.T, pl.TR);
+    launch_xe(s, ax_team_kernel<S, K, FU>, ax_team_kernel_f32<S, K, FU>, ax_team_kernel_u16<S, K, FU>,
+              dim3(pl.groups), dim3(kTmThreads), st, tm, s.N, s.M, s.mave, s.msig, x, part, fu, pl.T, pl.TR);
 }
 
 template <int S>

@@ -1,6 +1,6 @@
 // covariates.cpp — covariates of the probit model: ingest, the Newton fit of
 // their effects (vamp::Newton_method_cov, src/vamp_probit.cpp:525-617) around
-// the device sums of kernels.hip, and the entry points of include/vampomi.h.
+// the device sums of probit.hip, and the entry points of include/vampomi.h.
 //
 // The table is N-side data: every rank holds all of it, as it holds y, and
 // fits the effects itself from the same bits (no collective).

@@ -1,5 +1,5 @@
 // exp(x) correctly rounded in practice (double-double evaluation, one final
-// rounding).  Shared by the device (kernels.hip: the probit denoiser's erfcx,
+// rounding).  Shared by the device (probit.hip: the probit denoiser's erfcx,
 // src/utilities.cpp:293-363 via src/vamp_probit.cpp:469-488) and the CPU check
 // tests/exp_cr_check.c, so both run the same operations.  The includer defines
 // EXPCR_FN (the function qualifiers) before including this file; every

@@ -1,6 +1,11 @@
-// kdev.h — device helpers shared by the gfx950 kernel files (kernels.hip,
-// atax_team.hip, ingest.hip, assoc.hip).  Internal to libvampomi.
+// kdev.h — what the gfx950 kernel files (kernels.hip, atax_team.hip, vec.hip,
+// pcg.hip, probit.hip, ingest.hip, assoc.hip) share: the row-pair loads of X
+// and launch_xe over its three storages, the block sums and the finish of a
+// two-stage reduction, the CG decision, slot_sum, the counter-based
+// generators and the prelude's per-element expressions.  Internal to
+// libvampomi.
 #pragma once
+#include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -11,6 +16,22 @@ namespace vk {
 
 constexpr int kBlock = 256;  // 4 waves of 64
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// One launch for the three storages of X: k64, k32 and k16 are the same body
+// over double, float and 16-bit columns (the family's three __global__
+// wrappers); the one of the shard's element type gets (X, ld, args...), with
+// the timing events in its dispatch packet (hipExtLaunchKernelGGL: written by
+// the kernel's own dispatch, no extra marker packets around it).
+template <class K64, class K32, class K16, class... A>
+static void launch_xe(const Shard& s, K64 k64, K32 k32, K16 k16, dim3 grid, dim3 block, hipStream_t st,
+                      const Timing& tm, A... args) {
+    if (s.u16)
+        hipExtLaunchKernelGGL(k16, grid, block, 0, st, tm.start, tm.stop, 0, s.x16(), s.ld, args...);
+    else if (s.f32)
+        hipExtLaunchKernelGGL(k32, grid, block, 0, st, tm.start, tm.stop, 0, s.x32(), s.ld, args...);
+    else
+        hipExtLaunchKernelGGL(k64, grid, block, 0, st, tm.start, tm.stop, 0, s.x64(), s.ld, args...);
+}
 
 typedef double v2d __attribute__((ext_vector_type(2)));
 typedef float v2f __attribute__((ext_vector_type(2)));
@@ -194,6 +215,222 @@ __device__ inline void cg_decide_body(CgState* cs, const double* red, int it, Cg
 #pragma unroll
     for (int q = 0; q < 3 * kMaxRhs; ++q) r[q] = q < 3 * s.K ? red[q] : 0.0;
     cg_decide_from(s, cs, r, it, mirror, flag, seq, mask, pack);
+}
+
+// ---- block sums and the finish of a two-stage reduction (red_put above) ----
+// sum over a 256-thread block; every thread gets the result
+__device__ __forceinline__ double block_sum(double v, double* lds4) {
+    v = wave_sum(v);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) lds4[w] = v;
+    __syncthreads();
+    return ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
+}
+
+// red_put (above) publishes a block's partials; red_finish (below) takes the
+// ticket and sums them in block order (the protocol is described at red_put).
+
+// Block sums of nq <= NQ values at once, published with red_put at
+// part[base + q]: every wave reduces all values in registers, ONE barrier,
+// then thread q adds the four wave sums in wave order — the additions of nq
+// separate block_sum calls, with one barrier instead of 2*nq.
+template <int NQ>
+__device__ __forceinline__ void block_put_sums(double (&v)[NQ], int nq, const RedOut& ro, int64_t base) {
+    __shared__ double lds[4 * NQ];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+        if (q < nq) v[q] = wave_sum(v[q]);
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+            if (q < nq) lds[w * NQ + q] = v[q];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nq) {
+        const int q = threadIdx.x;
+        red_put(ro, base + q, ((lds[q] + lds[NQ + q]) + lds[2 * NQ + q]) + lds[3 * NQ + q]);
+    }
+}
+
+// (red_ticket, red_ticket_nowait, red_final and red_finish are static, not
+// inline: the inline hint changes the inliner's choices and with them scalar
+// instructions of the callers, profiles/kernel_split.md)
+// (red_finish's halves, for a launch that finishes two reductions: dots2)
+// every partial store of this block is acknowledged before the ticket moves;
+// true in the block that brings it to nblocks (block-uniform)
+[[maybe_unused]] static __device__ bool red_ticket(const RedOut& ro, int nblocks) {
+    __shared__ int is_last;
+    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+    __builtin_amdgcn_s_waitcnt(0);
+    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+    __syncthreads();
+    if (threadIdx.x == 0)
+        is_last = __hip_atomic_fetch_add(ro.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
+                  (unsigned)nblocks - 1;
+    __syncthreads();
+    return is_last;
+}
+
+// red_ticket for a block that published nothing: no wait for its own stores
+// (block-uniform; the barrier: every wave of the block is past its start)
+[[maybe_unused]] static __device__ bool red_ticket_nowait(const RedOut& ro, int nblocks) {
+    __shared__ int is_last;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        is_last = __hip_atomic_fetch_add(ro.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
+                  (unsigned)nblocks - 1;
+    __syncthreads();
+    return is_last;
+}
+
+// the last block's sums of the nblk blocks' partials at ro.part, into ro.out
+// (and keep); finish: then re-arm the ticket and store the host flag
+[[maybe_unused]] static __device__ void red_final(const RedOut& ro, int nq, int nblk, double* keep, bool finish) {
+    __shared__ double lds[4 * 8];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int q0 = 0; q0 < nq; q0 += 8) {
+        const int nc = nq - q0 < 8 ? nq - q0 : 8;
+        double s[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) s[c] = 0.0;
+        for (int b = threadIdx.x; b < nblk; b += kBlock) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c)
+                if (c < nc)
+                    s[c] += __hip_atomic_load(ro.part + (int64_t)b * nq + q0 + c, __ATOMIC_RELAXED,
+                                              __HIP_MEMORY_SCOPE_AGENT);
+        }
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+            if (c < nc) s[c] = wave_sum(s[c]);
+        __syncthreads();  // lds of the previous round consumed
+        if (lane == 0) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c)
+                if (c < nc) lds[w * 8 + c] = s[c];
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int c = 0; c < nc; ++c) {
+                const double v = ((lds[c] + lds[8 + c]) + lds[16 + c]) + lds[24 + c];
+                const int q = q0 + c;
+                double* dst = ro.out2 && q >= ro.split ? ro.out2 + (q - ro.split) : ro.out + q;
+                if (ro.flag || !finish)  // mapped host memory: written through, drained before the flag below
+                    __hip_atomic_store(dst, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                else
+                    *dst = v;
+                if (keep) keep[q0 + c] = v;
+            }
+    }
+    if (finish && threadIdx.x == 0) {
+        __hip_atomic_store(ro.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // host completion flag, after the results above have landed (drained
+        // write-through stores: no release fence, which would first write back
+        // this XCD's whole L2, MI355X_MICROARCH.md)
+        if (ro.flag) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __hip_atomic_store(ro.flag, ro.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+// The last block sums up to 8 results per round: each thread adds its
+// blocks' partials of every result (blocks in order), then each result is
+// wave-reduced and the four wave sums added in wave order — per result, the
+// operations of block_sum, so the sums are bitwise those of one block_sum per
+// result, with one barrier round per 8 results instead of one per result.
+// Returns true in the last block (after out[] is written; thread 0 wrote it).
+// keep (LDS, may be null): thread 0 also leaves the results there (a caller
+// that goes on with them in thread 0 then reads no global memory).
+[[maybe_unused]] static __device__ bool red_finish(const RedOut& ro, int nq, double* /*lds4*/, double* keep = nullptr) {
+    if (!red_ticket(ro, (int)gridDim.x)) return false;
+    red_final(ro, nq, (int)gridDim.x, keep, true);
+    return true;
+}
+
+// The per-slot A d partials summed over the slots: a workgroup takes 128
+// samples of one system (two per lane, 16-byte loads); wave w sums the slots
+// [w*ns/4, (w+1)*ns/4) in order with up to 32 loads in flight, wave 0 adds
+// the four wave sums in order.  cg_update's one-rank form (cg_update_kernel,
+// c.adpart) sums in exactly this order, so the two paths agree bit for bit.
+// (Every load of a round is issued before the first add: the adds stay in
+// slot order, so the round size changes the latency, not the bits.)
+// W: the largest round (32: 128 VGPRs of loads in flight; 8 for the few slots
+// of the large-N plans, so that cg_update's workgroups are not held to one per
+// CU by a round they never run)
+template <int W = 32>
+__device__ __forceinline__ v2d slot_sum(const double* src, int64_t ss, int t0, int t1) {
+    v2d acc = {0.0, 0.0};
+    int t = t0;
+    for (; W >= 32 && t + 32 <= t1; t += 32) {  // (C2, team of 2: 128 slots, 32 per wave, one round trip)
+        v2d x[32];
+#pragma unroll
+        for (int u = 0; u < 32; ++u) x[u] = *reinterpret_cast<const v2d*>(src + (t + u) * ss);
+#pragma unroll
+        for (int u = 0; u < 32; ++u) acc += x[u];
+    }
+    for (; W >= 16 && t + 16 <= t1; t += 16) {
+        v2d x[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) x[u] = *reinterpret_cast<const v2d*>(src + (t + u) * ss);
+#pragma unroll
+        for (int u = 0; u < 16; ++u) acc += x[u];
+    }
+    for (; t + 8 <= t1; t += 8) {
+        v2d x[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) x[u] = *reinterpret_cast<const v2d*>(src + (t + u) * ss);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc += x[u];
+    }
+    for (; t < t1; ++t) acc += *reinterpret_cast<const v2d*>(src + t * ss);
+    return acc;
+}
+
+// ---- the counter-based generators (synthetic data, the probes, probit_p1) ----
+__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ULL;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
+    return x ^ (x >> 31);
+}
+
+// Irwin-Hall(12) dyadic normal draw; same specification as the oracle's
+// orc_gauss_dyadic (oracle/vamp_oracle.c), exactly representable.
+__device__ __forceinline__ double gauss_dyadic(uint64_t seed, int64_t i, int64_t j) {
+    const uint64_t k = splitmix64(splitmix64(seed ^ 0x4741555353ULL) + (uint64_t)i);
+    uint64_t acc = 0;
+#pragma unroll
+    for (uint64_t t = 0; t < 3; ++t) {
+        const uint64_t h = splitmix64(k ^ (((uint64_t)j << 2) | t));
+        acc += (h & 0xFFFFULL) + ((h >> 16) & 0xFFFFULL) + ((h >> 32) & 0xFFFFULL) + (h >> 48);
+    }
+    return (double)(2 * acc + 12) * (1.0 / 131072.0) - 6.0;
+}
+
+__device__ __forceinline__ int bern_bit(uint64_t seed, int it, int64_t gidx) {
+    const uint64_t k = splitmix64(seed ^ 0xB5AD4ECEDA1CE2A9ULL);
+    const uint64_t h = splitmix64(k ^ (((uint64_t)(uint32_t)it << 40) ^ (uint64_t)gidx));
+    return (int)(h >> 63);
+}
+
+// The prelude at marker i (prelude_kernel in vec.hip, prelude_cg_init_kernel
+// in pcg.hip): r2, v, the probes bern and bern_next and the zero starts, from
+// the loaded x1[i], r1[i], atxy[i] and the scalars (p's, or the device's).
+// vv and bn: what went to p.v[i] and p.bern[i].
+__device__ __forceinline__ void prelude_at(const Prelude& p, int64_t i, double x1, double r1, double atxy, double eta1,
+                                           double gam1, double gam2, double gamw, double& vv, double& bn) {
+    const double r2 = (eta1 * x1 - gam1 * r1) / gam2;  // lincomb_div's expression
+    p.r2[i] = r2;
+    vv = gamw * atxy + gam2 * r2;                      // axpby's
+    p.v[i] = vv;
+    bn = (double)(2 * bern_bit(p.seed, p.it, p.S + i) - 1) / p.sqrtMt;
+    p.bern[i] = bn;
+    if (p.bern_next) p.bern_next[i] = (double)(2 * bern_bit(p.seed, p.it + 1, p.S + i) - 1) / p.sqrtMt;
+    if (p.zero[0]) p.zero[0][i] = 0.0;
+    if (p.zero[1]) p.zero[1][i] = 0.0;
 }
 
 }  // namespace vk

@@ -18,7 +18,7 @@ constexpr int kRedBlocks = 1024;  // max partial blocks of a reduction
 struct CPtrs { const double* p[kMaxRhs]; };
 // optional HIP events recorded by a launch's own dispatch (hipExtLaunchKernelGGL)
 struct Timing { hipEvent_t start = nullptr, stop = nullptr; };
-// Destination of a fused two-stage reduction (see red_finish in kernels.hip):
+// Destination of a fused two-stage reduction (see red_finish in kdev.h):
 // per-block partials in part, the final sums in out[0..nq) (device memory or
 // mapped host memory), ticket a zeroed device counter the kernel re-arms;
 // flag (may be null): the last block stores seq there (system scope, after out);
