@@ -647,7 +647,8 @@ typedef struct {
     int64_t host_syncs;
     vampomi_kernel_stat loo;      /* association-test pass (vampomi_assoc_loo) */
     vampomi_kernel_stat op;       /* one-pass CG operator (A^T q and A d, batch_rhs 4) */
-    vampomi_kernel_stat op_k[4];  /* index K-1 for K = 1, 2 systems; index 3: the head-start launch
+    vampomi_kernel_stat op_k[4];  /* index K-1 for K = 1, 2 systems; index 2: launches with a third
+                                     operator system; index 3: the head-start launch
                                      (one system + 3 plain A.x right-hand sides, pcg.cpp) */
     vampomi_kernel_stat coll;     /* RCCL all-reduces (several ranks): launches, bytes; with timing
                                      on, HIP events on the stream around each (its time on the
@@ -736,6 +737,15 @@ vampomi_status vampomi_dev_op_plan(int64_t N, int64_t M, int cus, int variant, i
  * VAMPOMI_ERR_ARG if there is no such team plan (or it is the whole-column
  * kernel's). */
 vampomi_status vampomi_dev_op_lds(int64_t N, int64_t M, int cus, int variant, int K, int64_t* out);
+/* The plan of launches with a THIRD operator system (vampomi_dev_op_apply3)
+ * beside the plan vampomi_dev_op_plan gives for the same arguments, no device
+ * needed: team size T (2..16), S, TR, grid, the team kernel configuration cfg,
+ * nslots, the kernel name, and (lds not null) its dynamic LDS layout with
+ * three systems as vampomi_dev_op_lds gives it.  The same for every storage of
+ * X.  VAMPOMI_ERR_ARG if there is none (whole-column and T = 1 plans, N beyond
+ * 16 members' rows). */
+vampomi_status vampomi_dev_op3_plan(int64_t N, int64_t M, int cus, int variant, int* T, int* S, int* TR, int* grid,
+                                    int* cfg, int64_t* nslots, char* name, int cap, int64_t* lds);
 /* Experiment builds only (atax_team.hip compiled with TM_TS=1, and
  * VAMPOMI_OP_TS=1 set before the context's first operator use): the last
  * operator launch's per-workgroup {start, end, XCC id, HW_ID} (s_memrealtime
@@ -765,6 +775,15 @@ vampomi_status vampomi_dev_mem_plan_storage(int64_t N, int64_t Mt, int nranks, i
 vampomi_status vampomi_dev_op_apply(vampomi_ctx* ctx, int K, const double* ar, const double* qo, const double* p,
                                     const double* z, const double* beta, double diag, double tau, double gam2,
                                     double* d, double* ad, double* dp);
+/* One launch with THREE operator systems (one rank; VAMPOMI_ERR_ARG where the
+ * context's plan has no 3-system plan beside it): systems 0 and 1 as
+ * vampomi_dev_op_apply takes them with K = 2, and in the third slot the
+ * alternate system on ar3 (N) and p3 (M) with diag = tau = 1, gam2 = 0 and no
+ * direction update: d_2 = A^T ar3, ad_2 = A d_2.  d: 3 x M, ad: 3 x N, dp: 2
+ * (the third slot has no <d, p>). */
+vampomi_status vampomi_dev_op_apply3(vampomi_ctx* ctx, const double* ar, const double* qo, const double* p,
+                                     const double* z, const double* beta, double diag, double tau, double gam2,
+                                     const double* ar3, const double* p3, double* d, double* ad, double* dp);
 
 #ifdef __cplusplus
 }

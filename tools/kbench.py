@@ -69,6 +69,13 @@ if "op" in only:  # the one-pass CG operator (A^T q and A d from one read of X),
             _lib.check(lib.vampomi_dev_time_pass(d.ctx, 3, K, reps, C.byref(ms)))
             b = 8.0 * N * Mt + 8.0 * K * N + 8.0 * (2 + K) * Mt
             row[f"K{K}"] = {"us": round(ms.value * 1e3, 1), "GBs": round(b / (ms.value * 1e-3) / 1e9, 1)}
+        # a launch with a third operator system, on the 3-system plan beside this one (where there is one)
+        ms = C.c_double()
+        if lib.vampomi_dev_time_pass(d.ctx, 3, 3, 2, C.byref(ms)) == 0:
+            _lib.check(lib.vampomi_dev_time_pass(d.ctx, 3, 3, reps, C.byref(ms)))
+            b = 8.0 * N * Mt + 8.0 * 3 * N + 8.0 * (2 + 3) * Mt
+            row["K3"] = {"kernel": d.kernel_name(3, 3), "us": round(ms.value * 1e3, 1),
+                         "GBs": round(b / (ms.value * 1e-3) / 1e9, 1)}
         res["op"][v] = row
         print("op", v, json.dumps(row), flush=True)
     d.set_variant(3, -1)

@@ -637,6 +637,33 @@ class Data:
                                              _dp(d), _dp(ad), _dp(dp)))
         return d[:, : self.M], ad, dp
 
+    def op_apply3(self, ar, p, diag: float, tau: float, gam2: float, ar3, p3, z=None, qo=None, beta=None):
+        """Development hook: one operator launch with three systems
+        (vampomi_dev_op_apply3): systems 0 and 1 as op_apply takes them with
+        K = 2, and in the third slot the alternate system on ar3 (N) and p3 (M)
+        (diag = tau = 1, gam2 = 0, no direction update).  Returns (d, A d,
+        <d, p>): 3 x M, 3 x N and the two systems' <d, p>."""
+        ar = np.ascontiguousarray(ar, dtype=np.float64)
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        ar3 = np.ascontiguousarray(ar3, dtype=np.float64)
+        p3 = np.ascontiguousarray(p3, dtype=np.float64)
+        if ar.shape != (2, self.N) or p.shape != (2, self.M) or ar3.shape != (self.N,) or p3.shape != (self.M,):
+            raise ValueError("ar must be 2 x N, p 2 x M, ar3 N and p3 M")
+        fz = z is not None
+        if fz:
+            z = np.ascontiguousarray(z, dtype=np.float64)
+            qo = np.ascontiguousarray(qo, dtype=np.float64)
+            beta = np.ascontiguousarray(beta, dtype=np.float64)
+            if z.shape != (2, self.M) or qo.shape != (2, self.N) or beta.shape != (2,):
+                raise ValueError("z must be 2 x M, qo 2 x N and beta 2")
+        d = np.zeros((3, max(self.M, 1)))
+        ad = np.zeros((3, self.N))
+        dp = np.zeros(2)
+        check(self._lib.vampomi_dev_op_apply3(self.ctx, _dp(ar), _dp(qo) if fz else None, _dp(p),
+                                              _dp(z) if fz else None, _dp(beta) if fz else None, diag, tau, gam2,
+                                              _dp(ar3), _dp(p3), _dp(d), _dp(ad), _dp(dp)))
+        return d[:, : self.M], ad, dp
+
     def read_ceiling(self, reps: int = 9) -> dict:
         """The HBM read ceiling on this device for this shard (vampomi_dev_read_ceiling):
         a pure read stream of the resident matrix, the faster variant's median."""

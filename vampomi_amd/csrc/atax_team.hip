@@ -265,7 +265,8 @@ __device__ __forceinline__ Tp* tm_chk(Tp* p, const void* lo, const void* hi, uns
 
 // the systems' pointers and scalars per slot: OpArgs', or the alternate
 // system's in slot alt (OpAlt: diag = tau = 1, gam2 = 0; its raw product t
-// equals its d but for the sign of a zero, and d's store is the later one)
+// equals its d but for the sign of a zero, and d's store is the later one).
+// A third slot (K = kOpSys) is always the alternate's.
 template <int K>
 struct TmSlots {
     const double* ar[K];
@@ -282,7 +283,7 @@ __device__ __forceinline__ TmSlots<K> tm_slots(const OpArgs& a, int alt) {
         // one indexed read of the launch's slot table per value (the index is
         // opaque, so that the compiler does not load both candidates and hold
         // them in scalar registers until it selects)
-        int idx = k == alt ? kOpMaxK : k;
+        int idx = k == alt || k >= kOpMaxK ? kOpMaxK : k;
         asm volatile("" : "+s"(idx));
         const OpAlt::Slot& t = a.alt.tab[idx];
         s.ar[k] = t.ar;
@@ -336,6 +337,14 @@ __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t
     }
     const double* beta = a.fold.on ? s_beta : a.beta;
     static_assert(K + KP <= kMaxRhs, "partial slots per team");
+    // K = kOpSys (3): two CG systems and the alternate system in slot 2, which
+    // has no fused direction update and no <d,p>.  KD: the systems with a
+    // <d,p>; KG: the systems the granule block is laid out for; GW: lanes per
+    // system in the hand-off wave's member sum (T <= GW)
+    static_assert(K <= kOpSys && (K <= kOpMaxK || (COMM && KP == 0)), "a third system: team plans only");
+    constexpr int KD = K < kOpMaxK ? K : kOpMaxK;
+    constexpr int KG = K > kOpMaxK ? K : kOpMaxK;
+    constexpr int GW = K > 2 ? 16 : 32;
     // The pre-step (kernels.h OpAlt): the lowest slot whose system has stopped,
     // if this solve has made none yet, runs on the alternate system instead.
     // Uniform over the grid: every wave evaluates it from the same scalar
@@ -381,7 +390,7 @@ __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t
     const int64_t mb = ilv ? team : (int64_t)team * M / nteams;
     const int n = (int)(ilv ? (M - team + nteams - 1) / nteams : (int64_t)(team + 1) * M / nteams - mb);
     const int64_t nmax = (M + nteams - 1) / nteams;  // granule rows per team
-    const int64_t gwords = (M + gridDim.x) * kOpMaxK * T * 2;  // the granule block (OpArgs.xg)
+    const int64_t gwords = (M + gridDim.x) * KG * T * 2;  // the granule block (OpArgs.xg)
     const int64_t r0 = (int64_t)member * TR;
     const int nrows = (int)(N - r0 < TR ? N - r0 : TR);  // >= 1 (op_plan)
     constexpr bool QFULL = tm_qfull(K, S, COMM, E);
@@ -416,11 +425,12 @@ __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t
         // granules of step m at xg + m * nq2: the team's m-th column
         unsigned long long* xg = a.xg + (int64_t)team * nmax * nq * 2;
         unsigned long long* dummy = a.xg + gwords + (int64_t)blockIdx.x * 2 * K;
-        // lane 32k + j reads member j's granule of system k (j < T), so one
-        // fixed 32-lane butterfly sums every team size (the zeros of lanes
-        // j >= T leave the sums' bits unchanged); other lanes re-read granule 0
-        const bool qv = (lane >> 5) < K && (lane & 31) < T;
-        const int ql2 = qv ? 2 * ((lane >> 5) * T + (lane & 31)) : 0;
+        // lane GW*k + j reads member j's granule of system k (j < T), so one
+        // fixed GW-lane butterfly sums every team size (the zeros of lanes
+        // j >= T leave the sums' bits unchanged); other lanes re-read granule 0.
+        // GW = 32 holds two systems, 16 three (T <= 16, atax_team)
+        const bool qv = (lane / GW) < K && (lane % GW) < T;
+        const int ql2 = qv ? 2 * ((lane / GW) * T + (lane % GW)) : 0;
         const int nq2 = 2 * nq;          // words per column of the granule block
         const int csi = (int)cs;         // column stride (1 or nteams)
         const unsigned tag = a.tag;
@@ -429,13 +439,13 @@ __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             if (lane == 1 + k) scp = sl.p[k];
-            if (lane == 1 + K + k && ((fuse >> k) & 1)) scp = a.z.p[k];
+            if (k < kOpMaxK && lane == 1 + K + k && ((fuse >> k) & 1)) scp = a.z.p[k];
         }
         scp += mb;  // column m (relative) is scp[m * cs]
         double bk[K], dpacc[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            bk[k] = ((fuse >> k) & 1) ? beta[k] : 0.0;
+            bk[k] = k < kOpMaxK && ((fuse >> k) & 1) ? beta[k] : 0.0;
             dpacc[k] = 0.0;
         }
         v4u pl[RING];
@@ -449,7 +459,7 @@ __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t
             // (sc1).  Each member posts {XCC id, tag} write-through, then reads all T.
             bool l2 = false;
             {
-                unsigned long long* hdr = a.xg + gwords + (int64_t)gridDim.x * 2 * kOpMaxK + (int64_t)team * T;
+                unsigned long long* hdr = a.xg + gwords + (int64_t)gridDim.x * 2 * KG + (int64_t)team * T;
                 unsigned xcc;
                 asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
                 xcc &= 0xf;
@@ -513,7 +523,7 @@ __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t
                         if (dbg & 512) {  // timing experiment: the ds_bpermute butterfly
                             for (int o = T >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
                         } else if (!(dbg & 256)) {
-                            v = group_sum<32>(v);  // the T members of system k in lanes 32k.., fixed order
+                            v = group_sum<GW>(v);  // the T members of system k in lanes GW*k.., fixed order
                         }
                         // d of column cf (src/vamp.cpp:656-659, data::ATx's scaling src/data.cpp:327-330)
                         const double scv = __builtin_bit_cast(double, ((unsigned long long)sc.y << 32) | sc.x);
@@ -525,10 +535,10 @@ __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t
                         double tsc[K], dval[K], pdir[K];
 #pragma unroll
                         for (int k = 0; k < K; ++k) {
-                            double t = sg * readlane_d(v, 32 * k);  // sigma_inv * dpa
+                            double t = sg * readlane_d(v, GW * k);  // sigma_inv * dpa
                             t *= a.scale;                           // ATx[mloc] *= 1/sqrt(N)
                             double p = readlane_d(scv, 1 + k);
-                            if ((fuse >> k) & 1) p = readlane_d(scv, 1 + K + k) + bk[k] * p;  // p = z + beta p
+                            if (k < kOpMaxK && ((fuse >> k) & 1)) p = readlane_d(scv, 1 + K + k) + bk[k] * p;  // p = z + beta p
                             double val = t * sl.tau[k];  // res[i] *= tau
                             val += sl.gam2[k] * p;       // res[i] += gam2 * v[i]
                             tsc[k] = t;
@@ -558,7 +568,7 @@ __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t
                         const v4u gr = {(unsigned)u, tag, (unsigned)(u >> 32), tag};
                         unsigned long long* dst =
                             tm_chk(real ? xg + ((int64_t)m * nq2 + (lane * T + member) * 2) : dummy + 2 * lane, a.xg,
-                                   a.xg + gwords + (int64_t)gridDim.x * 2 * kOpMaxK, 512, a.err);
+                                   a.xg + gwords + (int64_t)gridDim.x * 2 * KG, 512, a.err);
                         if (l2)
                             tm_publish_l2(dst, gr);
                         else
@@ -578,7 +588,7 @@ __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t
         // before the barrier after which wave 0 takes the ticket
         if (lane == 0) {
 #pragma unroll
-            for (int k = 0; k < K; ++k) red_put(a.ro, (int64_t)blockIdx.x * K + k, dpacc[k]);
+            for (int k = 0; k < KD; ++k) red_put(a.ro, (int64_t)blockIdx.x * KD + k, dpacc[k]);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -600,7 +610,7 @@ __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t
                 if (jl + h < nrows) {
                     const int64_t j = r0 + jl + h;
                     q = sl.ar[k][j] / sl.diag[k];
-                    if ((fuse >> k) & 1) q = q + beta[k] * a.qo.p[k][j];
+                    if (k < kOpMaxK && ((fuse >> k) & 1)) q = q + beta[k] * a.qo.p[k][j];
                 }
                 q_lds[k * QS + jl + h] = q;
             }
@@ -608,7 +618,7 @@ __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t
     }
     double bk[K];
 #pragma unroll
-    for (int k = 0; k < K; ++k) bk[k] = ((fuse >> k) & 1) ? beta[k] : 0.0;
+    for (int k = 0; k < K; ++k) bk[k] = k < kOpMaxK && ((fuse >> k) & 1) ? beta[k] : 0.0;
     // per-lane source of the column's scalars: lane 0 mave, 1 msig, 2.. p_k,
     // 2+K.. z_k, 2+2K.. the plain right-hand sides x_kp
     const double* pkp = mave;
@@ -616,7 +626,7 @@ __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         if (lane == 2 + k) pkp = sl.p[k];
-        if (lane == 2 + K + k && ((fuse >> k) & 1)) pkp = a.z.p[k];
+        if (k < kOpMaxK && lane == 2 + K + k && ((fuse >> k) & 1)) pkp = a.z.p[k];
     }
 #pragma unroll
     for (int k = 0; k < KP; ++k)
@@ -738,11 +748,11 @@ __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t
                 }
             }
         }
-        if (K == 2) {
+        if (K >= 2) {
             // reduce-scatter: one permlane32 swap leaves k = 0 in lanes 0-31
             // and k = 1 in lanes 32-63, then sums within each half
             double r0, r1;
-            swap32(v[0], v[K - 1], r0, r1);
+            swap32(v[0], v[K >= 2 ? 1 : 0], r0, r1);
             double keep = r0 + r1;
             if (dbg & 512) {  // timing experiment: the ds_bpermute butterfly
                 for (int o = 16; o > 0; o >>= 1) keep += __shfl_xor(keep, o, 64);
@@ -750,6 +760,10 @@ __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t
                 keep = group_sum<32>(keep);
             }
             if ((lane & 31) == 0) s_part[(par * CW + wave) * K + (lane >> 5)] = keep;
+            if constexpr (K == 3) {  // the third system: a whole-wave sum of its own
+                if (!(dbg & 4)) v[K - 1] = group_sum<64>(v[K - 1]);
+                if (lane == 0) s_part[(par * CW + wave) * K + K - 1] = v[K - 1];
+            }
         } else {
             if (!(dbg & 4)) v[0] = group_sum<64>(v[0]);
             if (lane == 0) s_part[(par * CW + wave) * K] = v[0];
@@ -771,7 +785,7 @@ __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t
                 double t = sg * tot[k];  // sigma_inv * dpa
                 t *= a.scale;            // ATx[mloc] *= 1/sqrt(N)
                 double p = readlane_d(pk[slot], 2 + k);
-                if ((fuse >> k) & 1) p = readlane_d(pk[slot], 2 + K + k) + bk[k] * p;  // p = z + beta p
+                if (k < kOpMaxK && ((fuse >> k) & 1)) p = readlane_d(pk[slot], 2 + K + k) + bk[k] * p;  // p = z + beta p
                 double val = t * sl.tau[k];  // res[i] *= tau
                 val += sl.gam2[k] * p;       // res[i] += gam2 * v[i]
                 if (own) {
@@ -866,9 +880,9 @@ __device__ __forceinline__ void atax_team_body(const XE* __restrict__ X, int64_t
         __syncthreads();
     } else if (threadIdx.x == 0) {
 #pragma unroll
-        for (int k = 0; k < K; ++k) red_put(a.ro, (int64_t)blockIdx.x * K + k, dpacc[k]);
+        for (int k = 0; k < KD; ++k) red_put(a.ro, (int64_t)blockIdx.x * KD + k, dpacc[k]);
     }
-    if (wave == 0) ticket_sum_blocks<K>(a.ro);
+    if (wave == 0) ticket_sum_blocks<KD>(a.ro);
 #if TM_TS
     if (a.ts && threadIdx.x == 0) {
         unsigned xcc, hw;
@@ -1131,8 +1145,37 @@ bool team_plan(int64_t N, int64_t M, int cus, int T, int cfg, OpPlan* out) {
     return true;
 }
 
+// the most loads per lane per column the 3-system kernel (K = kOpSys) is
+// instantiated for, per configuration (0: none): a third accumulator set costs
+// 4*S registers beside the ring (register counts and spills checked with
+// tools/regcheck.py: configuration 2 at S = 3 198 VGPRs, configuration 4 at
+// S = 4 206; at S = 5 the fp64 kernel spills, and every storage has the same plans)
+static constexpr int tm_sys3_maxS(int cfg) { return cfg == 2 ? 3 : cfg == 4 ? 4 : 0; }
+static constexpr int kTmSys3MaxT = 16;  // three groups of 16 lanes in the hand-off wave's member sum
+
+bool team_sys3_ok(const OpPlan& pl) {
+    if (pl.cfg < 0 || pl.cfg >= kTmNCfg || pl.T < 2 || pl.T > kTmSys3MaxT || pl.S < 1 || pl.S > tm_sys3_maxS(pl.cfg))
+        return false;
+    const TmCfg& c = kTmCfg[pl.cfg];
+    return tm_lds(kOpSys, pl.S, c.comm, c.E, pl.TR).words * 8 <= kTmLdsMaxBytes;
+}
+
+bool team_sys3_plan(int64_t N, int64_t M, int cus, const OpPlan& main, OpPlan* out) {
+    if (main.T < 2) return false;  // (T = 1 plans keep two systems per launch)
+    for (int T = main.T; T <= kTmSys3MaxT; T *= 2) {
+        for (int cfg : {2, 4}) {
+            OpPlan p{};
+            if (!team_plan(N, M, cus, T, cfg, &p) || !team_sys3_ok(p)) continue;
+            *out = p;
+            return true;
+        }
+    }
+    return false;
+}
+
 bool team_lds_layout(const OpPlan& pl, int64_t N, int K, int64_t out[6]) {
-    if (pl.T < 1 || pl.cfg < 0 || pl.cfg >= kTmNCfg || K < 1 || K > kOpMaxK || N < 1) return false;
+    if (pl.T < 1 || pl.cfg < 0 || pl.cfg >= kTmNCfg || K < 1 || N < 1) return false;
+    if (K > kOpMaxK && !(K == kOpSys && team_sys3_ok(pl))) return false;
     const TmCfg& c = kTmCfg[pl.cfg];
     const TmLds l = tm_lds(K, pl.S, c.comm, c.E, std::min<int64_t>(pl.TR, N));
     out[0] = kTmLdsHead;
@@ -1205,7 +1248,7 @@ static constexpr int tm_plain_maxS(int cfg) {
 template <int K, int C, int S, bool PL>
 static hipError_t launch_tm_if(const Shard& s, const OpPlan& pl, const OpArgs& a, hipStream_t st, const Timing& tm,
                                const int* gate, int* occ) {
-    if constexpr (S <= (PL ? tm_plain_maxS(C) : kTmCfg[C].maxS))
+    if constexpr (S <= (PL ? tm_plain_maxS(C) : K == kOpSys ? tm_sys3_maxS(C) : kTmCfg[C].maxS))
         return launch_tm<K, S, C, PL>(s, pl, a, st, tm, gate, occ);
     return hipErrorInvalidValue;
 }
@@ -1250,6 +1293,13 @@ static hipError_t launch_tm_c(const Shard& s, const OpPlan& pl, const OpArgs& a0
             default: return hipErrorInvalidValue;
         }
     }
+    if constexpr (K == kOpSys) {  // the configurations team_sys3_plan selects
+        switch (pl.cfg) {
+            case 2: return launch_tm_s<K, 2, false>(pl.S, s, pl, a, st, tm, gate, occ);
+            case 4: return launch_tm_s<K, 4, false>(pl.S, s, pl, a, st, tm, gate, occ);
+            default: return hipErrorInvalidValue;
+        }
+    }
     switch (pl.cfg) {
         case 0: return launch_tm_s<K, 0, false>(pl.S, s, pl, a, st, tm, gate, occ);
         case 1: return launch_tm_s<K, 1, false>(pl.S, s, pl, a, st, tm, gate, occ);
@@ -1271,6 +1321,13 @@ hipError_t atax_team(const Shard& s, const OpPlan& pl, int K, const OpArgs& a, h
     switch (K) {
         case 1: e = launch_tm_c<1>(s, pl, a, st, tm, gate); break;
         case 2: e = launch_tm_c<2>(s, pl, a, st, tm, gate); break;
+        case kOpSys:
+            // the third slot is the alternate system's: never with a folded
+            // decision, a slot rule of its own or a fused third direction
+            if (!team_sys3_ok(pl) || a.fold.on || a.alt.cs || (a.fuse >> kOpMaxK) || !a.alt.ar || !a.alt.p || !a.alt.d)
+                return hipErrorInvalidValue;
+            e = launch_tm_c<kOpSys>(s, pl, a, st, tm, gate);
+            break;
         default: break;
     }
     if (e != hipSuccess) return e;
@@ -1395,6 +1452,7 @@ int team_occupancy(const OpPlan& pl, int K, int ek) {
     switch (K) {
         case 1: e = launch_tm_c<1>(s, pl, a, nullptr, Timing{}, nullptr, &occ); break;
         case 2: e = launch_tm_c<2>(s, pl, a, nullptr, Timing{}, nullptr, &occ); break;
+        case kOpSys: e = team_sys3_ok(pl) ? launch_tm_c<kOpSys>(s, pl, a, nullptr, Timing{}, nullptr, &occ) : e; break;
         case 1 + kTmPlain: e = launch_tm_c<1, true>(s, pl, a, nullptr, Timing{}, nullptr, &occ); break;
         default: break;
     }

@@ -173,7 +173,7 @@ struct vampomi_ctx {
     double* op_part = nullptr;  // opp.nslots x kMaxRhs x ld partial A d
     int64_t op_part_slots = 0;
     double* op_nvec = nullptr;  // 3 x kMaxRhs x ld + 16: A r, q = A p, A d (+ <d,p> tail)
-    unsigned long long* op_xg = nullptr;  // team hand-off granules (M x kOpMaxK x T x 2), zeroed once
+    unsigned long long* op_xg = nullptr;  // team hand-off granules (M x kOpMaxK x T x 2; x kOpSys on opp3), zeroed once
     size_t op_xg_words = 0;
     unsigned op_tag = 0;        // the last team launch's tag
     // the head-start launch (pcg.cpp): its plan and whether it runs (default
@@ -183,9 +183,15 @@ struct vampomi_ctx {
     bool hs_ok = false;       // the head start runs (hs_on included; agreed on several ranks)
     bool hs_on = true;
     bool hs_on_req = true;
+    // launches with a third operator system (kernels.h kOpSys; op_dev with
+    // K = 3): their plan, and whether it exists and fits this device
+    vk::OpPlan opp3{};
+    bool sys3_ok = false;
     // the pre-step (HeadStart below): 0 off, 1 on at any size, 2 auto (one
     // rank, the linear model, the head start on and an X shard of at least
-    // kPreMinBytes); VAMPOMI_PRESTEP or vampomi_dev_set_variant(c, 7, v)
+    // kPreMinBytes); 3: mode 1 with two pre-steps per solve in a third
+    // operator slot where a 3-system plan exists (else mode 1);
+    // VAMPOMI_PRESTEP or vampomi_dev_set_variant(c, 7, v)
     int pre_mode = 2;
     unsigned long long pre_seq = 0;        // the last solve's token (OpAlt.token)
     int64_t pre_made_n = 0, pre_used_n = 0;  // since vampomi_vamp_begin (vampomi_dev_prestep_counts)
@@ -407,6 +413,21 @@ struct HeadStart {
     bool pre_offer = false;  // in: make them for the next solve (with xnext / axnext)
     bool pre_made = false;   // out: made (for xnext)
     bool pre_used = false;   // out: consumed
+    // Mode 3 (pre3; a 3-system plan exists, kernels.h kOpSys): no slot rule and
+    // no token.  Regular steps 0 and 1 of every solve are 3-system launches
+    // whose third slot forms T1 = A^T A xnext, U1 = A T1 (step 0) and
+    // T2 = A^T A T1, U2 = A T2 (step 1): a step that ran made its pre-step.
+    // With n_have = J in {0, 1, 2} this solve's system 0 composes its first J
+    // steps (vk::pre_compose, vk::pre_compose2), step J + 1 rides in the
+    // head-start pass, and the solve takes 1 + max(k1, k2 - 1 - J) passes (k2:
+    // the steps of system 0, the Onsager solve; k1: system 1's).
+    bool pre3 = false;
+    double* T2 = nullptr;      // M
+    double* U2 = nullptr;      // ld
+    double* rz_save = nullptr;  // device, 1 double: <r0,z0> of system 0 (PreCompose.rz_save)
+    int n_have = 0;  // in: the pre-steps in hand (pre_have: >= 1)
+    int n_made = 0;  // out
+    int n_used = 0;  // out
 };
 // how PcgArgs::pre's launch is queued (one rank)
 enum class PreMode { normal, ahead, queued };
@@ -464,6 +485,15 @@ constexpr int64_t kPreMinBytes = (int64_t)256 << 20;
 // whether the linear model's solves use the pre-step on this context (where
 // the head start is available): c->pre_mode resolved
 bool prestep_on(const vampomi_ctx* c);
+// ... and which rule: 0 off, 1 the slot rule (one pre-step per solve, in a
+// slot whose system has stopped), 3 two pre-steps per solve in a third
+// operator slot (a 3-system plan exists; op_prepare has run)
+int prestep_mode(const vampomi_ctx* c);
+// whether auto (2) asks for rule 3 where it turns the pre-step on (C2: 210.9-213.3 against 197.3-199.4
+// iterations/s under rule 1 in one job, profiles/prestep2.md)
+constexpr bool kPreAutoThird = true;
+// the context asks for rule 3 (pre_mode 3, or auto with kPreAutoThird), whether or not a 3-system plan exists
+bool prestep_wants3(const vampomi_ctx* c);
 // the device word a team launch sets when a hand-off timed out, and its host view
 unsigned* op_err_dev(vampomi_ctx* c);
 vampomi_status op_check_err(vampomi_ctx* c);

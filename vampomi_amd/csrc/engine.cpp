@@ -796,8 +796,9 @@ static size_t red_capacity(int64_t Mx) {
 
 // 8-byte words of the team hand-off granules: M columns x K x T granule pairs,
 // then a dummy pair per workgroup and K, then one XCD word per workgroup
-static size_t op_xg_words_for(int64_t Mx, const vk::OpPlan& p) {
-    return (size_t)(Mx + p.grid) * vk::kOpMaxK * (size_t)p.T * 2 + (size_t)p.grid * (2 * vk::kOpMaxK + 1);
+// (K: the systems the plan's launches lay the block out for: kOpMaxK, or kOpSys on the 3-system plan)
+static size_t op_xg_words_for(int64_t Mx, const vk::OpPlan& p, int K = vk::kOpMaxK) {
+    return (size_t)(Mx + p.grid) * K * (size_t)p.T * 2 + (size_t)p.grid * (2 * K + 1);
 }
 
 static vampomi_status op_plan_local(vampomi_ctx* c) {
@@ -823,8 +824,12 @@ static vampomi_status op_plan_local(vampomi_ctx* c) {
     // hold, only means the solves start without it)
     bool hs_ok = op_ok && vk::team_plain_plan(c->N, M, c->cus, c->opp, &c->opp_hs);
     if (hs_ok && (int64_t)vk::team_occupancy(c->opp_hs, 1 + vk::kOpPlain, c->ek()) * c->cus < c->opp_hs.grid) hs_ok = false;
+    // the 3-system plan: optional too (without it no launch carries a third system)
+    bool sys3_ok = op_ok && vk::team_sys3_plan(c->N, M, c->cus, c->opp, &c->opp3);
+    if (sys3_ok && (int64_t)vk::team_occupancy(c->opp3, vk::kOpSys, c->ek()) * c->cus < c->opp3.grid) sys3_ok = false;
     c->op_ok_mine = op_ok;
     c->hs_ok_mine = hs_ok;
+    c->sys3_ok = sys3_ok;
     if (!c->op_ts && std::getenv("VAMPOMI_OP_TS") && std::atoi(std::getenv("VAMPOMI_OP_TS"))) {
         HIPCHK(hipMalloc((void**)&c->op_ts, (size_t)4 * 8 * std::max(c->cus, 1) * 2));
         HIPCHK(hipMemsetAsync(c->op_ts, 0, (size_t)4 * 8 * std::max(c->cus, 1) * 2, c->st));
@@ -834,15 +839,17 @@ static vampomi_status op_plan_local(vampomi_ctx* c) {
         HIPCHK(hipMemsetAsync(c->op_nvec, 0, ((size_t)3 * vk::kMaxRhs * c->ld + 16) * 8, c->st));
     }
     if (op_ok) {
-        const int64_t slots = std::max<int64_t>(c->opp.nslots, hs_ok ? c->opp_hs.nslots : 0);
+        const int64_t slots =
+            std::max<int64_t>({c->opp.nslots, hs_ok ? c->opp_hs.nslots : 0, sys3_ok ? c->opp3.nslots : 0});
         if (slots > c->op_part_slots) {
             dev_free(c->op_part);
             STCHK(dev_alloc(&c->op_part, (size_t)slots * vk::kMaxRhs * c->ld));
             c->op_part_slots = slots;
         }
-        if (c->opp.T > 1 || (hs_ok && c->opp_hs.T > 1)) {
+        if (c->opp.T > 1 || (hs_ok && c->opp_hs.T > 1)) {  // (a 3-system plan only beside a main plan with T > 1)
             size_t words = c->opp.T > 1 ? op_xg_words_for(M, c->opp) : 0;
             if (hs_ok && c->opp_hs.T > 1) words = std::max(words, op_xg_words_for(M, c->opp_hs));
+            if (sys3_ok) words = std::max(words, op_xg_words_for(M, c->opp3, vk::kOpSys));
             if (words > c->op_xg_words) {
                 if (c->op_xg) (void)hipFree(c->op_xg);
                 c->op_xg = nullptr;
@@ -996,13 +1003,17 @@ vampomi_status op_check_err(vampomi_ctx* c) {
 vampomi_status op_dev(vampomi_ctx* c, int K, const vk::OpArgs& a, const int* gate, bool reduce, bool divide) {
     if (!c->have_X) return fail(VAMPOMI_ERR_STATE, "A before the methylation data was loaded");
     STCHK(op_prepare(c));
-    if (!c->op_ok || K < 1 || K > vk::kOpMaxK)
-        return fail(VAMPOMI_ERR_ARG, "one-pass operator: K <= 2 and a plan for N = " + std::to_string(c->N));
+    if (!c->op_ok || K < 1 || K > vk::kOpSys)
+        return fail(VAMPOMI_ERR_ARG, "one-pass operator: K <= 3 and a plan for N = " + std::to_string(c->N));
+    // K = kOpSys: two systems and the alternate system (a.alt) on the 3-system plan, one rank only
+    if (K == vk::kOpSys && (!c->sys3_ok || c->use_comm))
+        return fail(VAMPOMI_ERR_ARG, "one-pass operator: no 3-system plan for N = " + std::to_string(c->N));
+    const vk::OpPlan& pl = K == vk::kOpSys ? c->opp3 : c->opp;
     double* ad = c->op_nvec + (int64_t)2 * vk::kMaxRhs * c->ld;
     vk::OpArgs x = a;
     x.part = c->op_part;
     x.scale = 1.0 / c->sqrtN;
-    if (c->opp.T > 1) {
+    if (pl.T > 1) {
         x.xg = c->op_xg;
         if (++c->op_tag == 0) ++c->op_tag;
         x.tag = c->op_tag;
@@ -1015,13 +1026,12 @@ vampomi_status op_dev(vampomi_ctx* c, int K, const vk::OpArgs& a, const int* gat
     x.ro = vk::RedOut{c->red_part, c->use_comm ? ad + (int64_t)K * c->ld : c->scal + SL_DP, c->ticket, nullptr, 0,
                       gate};
     TimedLaunch t = launch_stat(c, 3, K, pass_bytes(c, K), 2.0 * pass_flops(c, K));
-    STCHK(team_launch(c, c->opp.T,
-                      [&] { return vk::atax(c->shard(), c->opp, K, x, c->st, vk::Timing{t.a, t.b}, gate); }));
+    STCHK(team_launch(c, pl.T, [&] { return vk::atax(c->shard(), pl, K, x, c->st, vk::Timing{t.a, t.b}, gate); }));
     c->stats.a_passes_exec++;
     vk::Ptrs os{};
     for (int k = 0; k < K; ++k) os.p[k] = ad + (int64_t)k * c->ld;
     if (!c->use_comm) {
-        if (reduce) HIPCHK(vk::op_reduce(c->opp, K, c->N, c->ld, c->op_part, os, c->sqrtN, c->st, gate));
+        if (reduce) HIPCHK(vk::op_reduce(pl, K, c->N, c->ld, c->op_part, os, c->sqrtN, c->st, gate));
     } else {
         HIPCHK(vk::op_reduce(c->opp, K, c->N, c->ld, c->op_part, os, 0.0, c->st, gate));
         STCHK(allreduce_dev(c, ad, (size_t)K * c->ld + K));  // src/data.cpp:367
@@ -1245,7 +1255,7 @@ extern "C" vampomi_status vampomi_open(const vampomi_shard_desc* d, vampomi_ctx*
     if (const char* hv = std::getenv("VAMPOMI_HEADSTART")) c->hs_on = c->hs_on_req = std::atoi(hv) != 0;
     if (const char* pv = std::getenv("VAMPOMI_PRESTEP")) {
         const int v = std::atoi(pv);
-        if (v >= 0 && v <= 2) c->pre_mode = v;
+        if (v >= 0 && v <= 3) c->pre_mode = v;
     }
     const char* mode = std::getenv("VAMPOMI_COMM");
     if (c->use_comm && mode && std::strcmp(mode, "loopback") == 0) {
@@ -1758,7 +1768,7 @@ extern "C" vampomi_status vampomi_dev_set_variant(vampomi_ctx* c, int which, int
         c->hs_on_req = variant == 1;  // several ranks: applied and agreed at the next vampomi_vamp_begin
         if (!c->use_comm) c->hs_on = c->hs_on_req;
     } else if (which == 7) {  // the pre-step (pcg.cpp): 0 off, 1 on at any size, 2 auto
-        if (variant < 0 || variant > 2) return fail(VAMPOMI_ERR_ARG, "pre-step: 0, 1 or 2");
+        if (variant < 0 || variant > 3) return fail(VAMPOMI_ERR_ARG, "pre-step: 0, 1, 2 or 3");
         c->pre_mode = variant;
     } else if (which == 6) {  // several ranks: the host-free iteration tail (vamp.cpp, VAMPOMI_MR_TAIL): 0 off, 1 on
         if (variant != 0 && variant != 1) return fail(VAMPOMI_ERR_ARG, "multi-rank tail: 0 or 1");
@@ -1773,7 +1783,15 @@ extern "C" vampomi_status vampomi_dev_set_variant(vampomi_ctx* c, int which, int
 
 bool prestep_on(const vampomi_ctx* c) {
     if (c->use_comm || c->nranks != 1 || !c->hs_ok || c->pre_mode == 0) return false;
-    return c->pre_mode == 1 || std::max<int64_t>(c->M, 1) * c->ld * c->esize() >= kPreMinBytes;
+    return c->pre_mode == 1 || c->pre_mode == 3 ||
+           std::max<int64_t>(c->M, 1) * c->ld * c->esize() >= kPreMinBytes;
+}
+
+bool prestep_wants3(const vampomi_ctx* c) { return c->pre_mode == 3 || (c->pre_mode == 2 && kPreAutoThird); }
+
+int prestep_mode(const vampomi_ctx* c) {
+    if (!prestep_on(c)) return 0;
+    return prestep_wants3(c) && c->sys3_ok ? 3 : 1;
 }
 
 extern "C" vampomi_status vampomi_dev_prestep_counts(const vampomi_ctx* c, int64_t* made, int64_t* used) {
@@ -1784,13 +1802,14 @@ extern "C" vampomi_status vampomi_dev_prestep_counts(const vampomi_ctx* c, int64
 }
 
 extern "C" vampomi_status vampomi_dev_time_pass(vampomi_ctx* c, int which, int K, int reps, double* avg_ms) {
-    if (!c || !avg_ms || K < 1 || K > (which == 0 ? 4 : which == 1 ? 3 : which == 3 ? 2 : 1) || reps < 1)
+    if (!c || !avg_ms || K < 1 || K > (which == 0 ? 4 : which == 1 ? 3 : which == 3 ? 3 : 1) || reps < 1)
         return fail(VAMPOMI_ERR_ARG, "bad argument");
     if (!c->have_X) return fail(VAMPOMI_ERR_STATE, "no methylation data loaded");
     HIPCHK(hipSetDevice(c->device));
     if (which == 3) {
         STCHK(op_prepare(c));  // a timing hook: this rank's plan, no agreement
         if (!c->op_ok_mine) return fail(VAMPOMI_ERR_ARG, "no one-pass operator plan for this N");
+        if (K == vk::kOpSys && !c->sys3_ok) return fail(VAMPOMI_ERR_ARG, "no 3-system operator plan for this N");
     }
     const int64_t Mx = std::max<int64_t>(c->M, 1);
     vk::CPtrs in{};
@@ -1809,27 +1828,34 @@ extern "C" vampomi_status vampomi_dev_time_pass(vampomi_ctx* c, int which, int K
         else if (which == 1)
             HIPCHK(vk::atx(c->shard(), K, in, out, 1.0 / c->sqrtN, 0, 0.0, 0.0, vk::CPtrs{}, c->st, c->atx_variant));
         else if (which == 3) {  // the operator on q = nbuf/1, p = mbuf slots 0..1, d into slots 2..3
+            // (K = 3: the third system's p is slot 4, its d slot 5, on the 3-system plan)
+            const vk::OpPlan& pl = K == vk::kOpSys ? c->opp3 : c->opp;
             vk::OpArgs x{};
-            for (int k = 0; k < K; ++k) {
+            for (int k = 0; k < K && k < vk::kOpMaxK; ++k) {
                 x.ar.p[k] = c->nbuf + k * c->ld;
                 x.p.p[k] = c->mbuf + k * Mx;
                 x.d.p[k] = c->mbuf + (2 + k) * Mx;
+            }
+            if (K == vk::kOpSys) {
+                x.alt.ar = c->nbuf + 2 * c->ld;
+                x.alt.p = c->mbuf + 4 * Mx;
+                x.alt.d = c->mbuf + 5 * Mx;
             }
             x.diag = 1.0;
             x.scale = 1.0 / c->sqrtN;
             x.tau = 1.0;
             x.part = c->op_part;
             x.ro = vk::RedOut{c->red_part, c->scal + SL_DP, c->ticket, nullptr, 0, nullptr};
-            if (c->opp.T > 1) {
+            if (pl.T > 1) {
                 x.xg = c->op_xg;
                 if (++c->op_tag == 0) ++c->op_tag;
                 x.tag = c->op_tag;
                 x.err = op_err_dev(c);
             }
             x.dbg = std::getenv("VAMPOMI_OP_DBG") ? std::atoi(std::getenv("VAMPOMI_OP_DBG")) : 0;
-            if (c->opp.T > 1) x.err = op_err_dev(c);
+            if (pl.T > 1) x.err = op_err_dev(c);
             x.ts = c->op_ts;
-            STCHK(team_launch(c, c->opp.T, [&] { return vk::atax(c->shard(), c->opp, K, x, c->st); }));
+            STCHK(team_launch(c, pl.T, [&] { return vk::atax(c->shard(), pl, K, x, c->st); }));
         }
         else  // association pass: ymod = nbuf slot 0, x1 = mbuf slot 0, sums in mbuf slots 3..7
             HIPCHK(vk::loo_sums(c->shard(), c->nbuf, c->mbuf, c->sqrtN, c->mbuf + 3 * Mx, c->st, c->loo_variant));
@@ -1897,6 +1923,59 @@ extern "C" vampomi_status vampomi_dev_op_apply(vampomi_ctx* c, int K, const doub
     return op_check_err(c);
 }
 
+extern "C" vampomi_status vampomi_dev_op_apply3(vampomi_ctx* c, const double* ar, const double* qo, const double* p,
+                                                const double* z, const double* beta, double diag, double tau,
+                                                double gam2, const double* ar3, const double* p3, double* d,
+                                                double* ad, double* dp) {
+    constexpr int K = vk::kOpMaxK;
+    if (!c || !ar || !p || !ar3 || !p3 || !d || !ad || !dp || (z && (!qo || !beta)))
+        return fail(VAMPOMI_ERR_ARG, "bad argument");
+    if (c->use_comm) return fail(VAMPOMI_ERR_ARG, "vampomi_dev_op_apply3: one rank only");
+    HIPCHK(hipSetDevice(c->device));
+    STCHK(op_prepare(c));
+    if (!c->op_ok || !c->sys3_ok) return fail(VAMPOMI_ERR_ARG, "no 3-system operator plan for this N");
+    const int64_t Mx = std::max<int64_t>(c->M, 1);
+    double* AR = c->op_nvec;
+    double* Q = c->op_nvec + (int64_t)vk::kMaxRhs * c->ld;
+    // mbuf slots: p 0-1, d 2-3, z 4-5, the third system's p 6 and d 7; beta in nbuf
+    vk::OpArgs a{};
+    for (int k = 0; k < K; ++k) {
+        STCHK(stage_in(c, ar + k * c->N, c->N, VAMPOMI_MEM_HOST, AR + k * c->ld));
+        STCHK(stage_in(c, p + k * c->M, c->M, VAMPOMI_MEM_HOST, c->mbuf + k * Mx));
+        a.ar.p[k] = AR + k * c->ld;
+        a.p.p[k] = c->mbuf + k * Mx;
+        a.d.p[k] = c->mbuf + (2 + k) * Mx;
+        if (z) {
+            STCHK(stage_in(c, qo + k * c->N, c->N, VAMPOMI_MEM_HOST, Q + k * c->ld));
+            STCHK(stage_in(c, z + k * c->M, c->M, VAMPOMI_MEM_HOST, c->mbuf + (4 + k) * Mx));
+            a.qo.p[k] = Q + k * c->ld;
+            a.z.p[k] = c->mbuf + (4 + k) * Mx;
+        }
+    }
+    STCHK(stage_in(c, ar3, c->N, VAMPOMI_MEM_HOST, AR + K * c->ld));
+    STCHK(stage_in(c, p3, c->M, VAMPOMI_MEM_HOST, c->mbuf + 6 * Mx));
+    a.alt.ar = AR + K * c->ld;
+    a.alt.p = c->mbuf + 6 * Mx;
+    a.alt.d = c->mbuf + 7 * Mx;
+    if (z) {
+        STCHK(stage_in(c, beta, K, VAMPOMI_MEM_HOST, c->nbuf));
+        a.beta = c->nbuf;
+        a.fuse = (1 << K) - 1;
+    }
+    a.diag = diag;
+    a.tau = tau;
+    a.gam2 = gam2;
+    STCHK(op_dev(c, vk::kOpSys, a, nullptr));
+    const double* AD = c->op_nvec + (int64_t)2 * vk::kMaxRhs * c->ld;
+    for (int k = 0; k < vk::kOpSys; ++k) {
+        STCHK(stage_out(c, k < K ? c->mbuf + (2 + k) * Mx : c->mbuf + 7 * Mx, c->M, VAMPOMI_MEM_HOST, d + k * c->M));
+        STCHK(stage_out(c, AD + k * c->ld, c->N, VAMPOMI_MEM_HOST, ad + k * c->N));
+    }
+    HIPCHK(hipMemcpyAsync(dp, c->scal + SL_DP, (size_t)K * 8, hipMemcpyDeviceToHost, c->st));
+    STCHK(sync_stream(c, c->st));
+    return op_check_err(c);
+}
+
 // experiment builds (TM_TS=1, VAMPOMI_OP_TS=1): the last operator launch's
 // per-workgroup {start, end, XCC id, HW id}, 4 x grid words
 extern "C" vampomi_status vampomi_dev_op_timestamps(vampomi_ctx* c, unsigned long long* out, int cap, int* n) {
@@ -1938,8 +2017,27 @@ extern "C" vampomi_status vampomi_dev_op_plan(int64_t N, int64_t M, int cus, int
 
 extern "C" vampomi_status vampomi_dev_op_lds(int64_t N, int64_t M, int cus, int variant, int K, int64_t* out) {
     vk::OpPlan p{};
-    if (!out || !vk::op_plan(N, std::max<int64_t>(M, 1), cus, variant, &p) || !vk::team_lds_layout(p, N, K, out))
+    if (!out || K > vk::kOpMaxK || !vk::op_plan(N, std::max<int64_t>(M, 1), cus, variant, &p) ||
+        !vk::team_lds_layout(p, N, K, out))
         return fail(VAMPOMI_ERR_ARG, "no team plan with that system count");
+    return VAMPOMI_OK;
+}
+
+extern "C" vampomi_status vampomi_dev_op3_plan(int64_t N, int64_t M, int cus, int variant, int* T, int* S, int* TR,
+                                               int* grid, int* cfg, int64_t* nslots, char* name, int cap,
+                                               int64_t* lds) {
+    vk::OpPlan main{}, p{};
+    const int64_t Mx = std::max<int64_t>(M, 1);
+    if (!vk::op_plan(N, Mx, cus, variant, &main) || !vk::team_sys3_plan(N, Mx, cus, main, &p))
+        return fail(VAMPOMI_ERR_ARG, "no 3-system operator plan");
+    if (lds && !vk::team_lds_layout(p, N, vk::kOpSys, lds)) return fail(VAMPOMI_ERR_ARG, "no 3-system operator plan");
+    if (T) *T = p.T;
+    if (S) *S = p.S;
+    if (TR) *TR = p.TR;
+    if (grid) *grid = p.grid;
+    if (cfg) *cfg = p.cfg;
+    if (nslots) *nslots = p.nslots;
+    if (name && cap > 0) std::snprintf(name, (size_t)cap, "%s", vk::team_kernel_name(vk::kOpSys, p).c_str());
     return VAMPOMI_OK;
 }
 
@@ -1973,16 +2071,28 @@ extern "C" vampomi_status vampomi_dev_mem_plan_storage(int64_t N, int64_t Mt, in
     vk::OpPlan op{}, hs{};
     if (vk::op_plan(N, Mx, cus, vk::kOpDefault, &op)) {
         const bool h = vk::team_plain_plan(N, Mx, cus, op, &hs);
+        vk::OpPlan s3{};
+        const bool h3 = vk::team_sys3_plan(N, Mx, cus, op, &s3);
         add((int64_t)3 * vk::kMaxRhs * ld + 16, 8);    // op_nvec
-        add(std::max<int64_t>(op.nslots, h ? hs.nslots : 0) * vk::kMaxRhs * ld, 8);  // op_part
+        add(std::max<int64_t>({op.nslots, h ? hs.nslots : 0, h3 ? s3.nslots : 0}) * vk::kMaxRhs * ld, 8);  // op_part
         size_t w = op.T > 1 ? op_xg_words_for(Mx, op) : 0;
         if (h && hs.T > 1) w = std::max(w, op_xg_words_for(Mx, hs));
+        if (h3) w = std::max(w, op_xg_words_for(Mx, s3, vk::kOpSys));
         if (w) add((int64_t)w, 8);
     }
     for (int q = 0; q < 25; ++q) add(Mx, 8);           // VampRun M-vectors (15 + cgw[10])
     add(ld, 8), add((int64_t)vk::kMaxRhs * ld, 8), add((int64_t)vk::kMaxRhs * ld, 8), add(ld, 8);
     add(2 * ld, 8);                                    // abern (the head start, two slots)
     add(Mx, 8), add(ld + 2, 8);                        // the pre-step's T1 and U1 (+ its done word)
+    {   // rule 3's T2 and U2 (+ the saved <r0,z0>): allocated by the first solve that runs under rule 3, which
+        // the default (auto) does on one rank, in the linear model, from kPreMinBytes on, beside a 3-system plan
+        vk::OpPlan s3{};
+        const bool auto3 = kPreAutoThird && nranks == 1 && !probit && vk::op_plan(N, Mx, cus, vk::kOpDefault, &op) &&
+                           vk::team_sys3_plan(N, Mx, cus, op, &s3) &&
+                           Mx * ld * (storage == VAMPOMI_STORE_F32 ? 4 : storage == VAMPOMI_STORE_U16 ? 2 : 8) >=
+                               kPreMinBytes;
+        if (auto3) add(Mx, 8), add(ld + 2, 8);
+    }
     if (probit) {
         for (int q = 0; q < 3; ++q) add(ld, 8);
         for (int q = 0; q < 3; ++q) add(Mx, 8);
@@ -2012,6 +2122,11 @@ static std::string op_name(const vampomi_ctx* c, int K) {
         vk::OpPlan h{};
         if (!vk::team_plain_plan(c->N, std::max<int64_t>(c->M, 1), cus, p, &h)) return "(no head-start plan)";
         return vk::team_kernel_name(K, h, c->ek());
+    }
+    if (K == vk::kOpSys) {  // launches with a third operator system
+        vk::OpPlan t{};
+        if (!vk::team_sys3_plan(c->N, std::max<int64_t>(c->M, 1), cus, p, &t)) return "(no 3-system plan)";
+        return vk::team_kernel_name(K, t, c->ek());
     }
     return vk::op_kernel_name(K, p, c->ek());
 }

@@ -158,6 +158,11 @@ hipError_t atx(const Shard& s, int K, CPtrs u, Ptrs out, double scale, int mode,
 //    the rows of each column and hand the column dots over inside the launch
 //    (T = 1: no hand-off), for N up to 32 x 8 x 896 rows.
 constexpr int kOpMaxK = 2;
+// A team launch on a 3-system plan (team_sys3_plan) carries kOpMaxK CG systems
+// and, in a third slot, the alternate system of OpAlt (diag = tau = 1,
+// gam2 = 0, no fused direction update, no <d,p>): K = kOpSys.  Its d is
+// OpAlt.d and its A d partials are slot kOpMaxK of each team.
+constexpr int kOpSys = kOpMaxK + 1;
 // the head-start launch (pcg.cpp): one operator system plus kOpPlain plain
 // right-hand sides A x_kp from the same read of X (stats: K = 1 + kOpPlain)
 constexpr int kOpPlain = 3;
@@ -241,7 +246,9 @@ struct OpArgs {
     RedOut ro;          // <d_k, p_k> summed over the shard (K values)
     // team kernel with T > 1: hand-off granules ((M + grid) x kOpMaxK x T x 2
     // words, then 2 x kOpMaxK dummy words per workgroup, then one XCD word per
-    // workgroup; zeroed once), this launch's
+    // workgroup; kOpSys in place of kOpMaxK for a launch with K = kOpSys, which
+    // lays the same block out for three systems: every 8-byte word of the block
+    // carries its launch's tag in its high half under either layout; zeroed once), this launch's
     // tag (never 0, new every launch) and a mapped host word set when a
     // hand-off timed out
     unsigned long long* xg;
@@ -253,7 +260,8 @@ struct OpArgs {
               // 5 write-through hand-off even when the team shares an XCD, 11 no LDS q reads,
               // 12 no hand-off work (the hand-off wave only keeps the step barriers)
     OpFold fold;  // team kernels only (atax_team.hip)
-    OpAlt alt;    // team kernels only, never with fold.on or plain right-hand sides
+    OpAlt alt;    // team kernels only, never with fold.on or plain right-hand sides; K = kOpSys: the third
+                  // slot's system (ar, p, d), cs null
 };
 static_assert(sizeof(OpAlt::tab) / sizeof(OpAlt::Slot) == kOpMaxK + 1, "one entry per system and the alternate's");
 std::string op_kernel_name(int K, const OpPlan& pl, int ek = 0);
@@ -274,6 +282,14 @@ hipError_t atax_team_plain(const Shard& s, const OpPlan& pl, const OpArgs& a, hi
 // a team plan for the head-start kernel (the main plan's team size if its rows
 // fit, else larger teams); false: none (the solve starts without a head start)
 bool team_plain_plan(int64_t N, int64_t M, int cus, const OpPlan& main, OpPlan* out);
+// a team plan for launches with K = kOpSys systems: the main plan's team size
+// (at least 2, at most 16: the hand-off wave sums three systems in groups of
+// 16 lanes) if three accumulator sets fit the registers at its rows per
+// member, else larger teams.  A function of (N, M, cus, main) only, so every
+// storage of X has the same one.  false: none
+bool team_sys3_plan(int64_t N, int64_t M, int cus, const OpPlan& main, OpPlan* out);
+// whether pl can launch with K = kOpSys (a plan team_sys3_plan may return)
+bool team_sys3_ok(const OpPlan& pl);
 // out_k[j] = sum_b part[b][k0 + k][j] (slots in order); if div > 0 then /= div
 hipError_t op_reduce(const OpPlan& pl, int K, int64_t N, int64_t ld, const double* part, Ptrs out, double div,
                      hipStream_t st, const int* gate = nullptr, int k0 = 0);
@@ -810,7 +826,42 @@ struct PreCompose {
     double* S;         // M, may be null
     double* AD;        // N
     double diag, tau, gam2;
+    // (may be null) rz_save[0] = cs->rz[0], <r0,z0> before the composed step's
+    // decision replaces it: pre_compose2 forms the step's alpha from it
+    const CgState* cs = nullptr;
+    double* rz_save = nullptr;
 };
 hipError_t pre_compose(int64_t M, int64_t N, const PreCompose& a, const RedOut& ro, hipStream_t st);
+// The SECOND CG step's operator products of the same system, composed from
+// T1, T2 = A^T A T1, U1 = A T1 and U2 = A T2 after the composed first step
+// (pre_compose, then its cg_update), with no pass over X.  With alpha0 =
+// rz_save[0] / dp0[0] (cg_update's own expression on the same values),
+// beta0 = cs->beta[0], p0 = p as stored and p1 = z_i + beta0*p0_i (the
+// direction update the step's cg_update stores):
+//   w_i  = (tau*T2_i + gam2*T1_i)/diag                     (A^T A d0)
+//   S_i  = (T1_i - alpha0*w_i)/diag + beta0*(T1_i/diag)    (A^T A p1)
+//   d_i  = tau*S_i + gam2*p1_i
+//   q1_j = ar_j/diag + beta0*q_j                           (A p1, as cg_update forms it)
+//   AD_j = tau*((U1_j - alpha0*((tau*U2_j + gam2*U1_j)/diag))/diag + beta0*(U1_j/diag)) + gam2*q1_j
+// <d,p1> in ro.out[0] (dp0 may be ro.out: every block reads it before the
+// last one stores).  Gated on ro.gate; nothing if system 0 has stopped
+struct PreCompose2 {
+    const double* T1;  // M
+    const double* T2;  // M
+    const double* U1;  // N
+    const double* U2;  // N
+    const double* ar;  // N: A r1 (after the composed first step)
+    const double* q;   // N: q0 = A p0
+    const double* p;   // M: p0
+    const double* z;   // M: z1
+    double* d;         // M
+    double* S;         // M, may be null
+    double* AD;        // N
+    double diag, tau, gam2;
+    const CgState* cs;
+    const double* rz_save;
+    const double* dp0;
+};
+hipError_t pre_compose2(int64_t M, int64_t N, const PreCompose2& a, const RedOut& ro, hipStream_t st);
 
 }  // namespace vk

@@ -13,7 +13,8 @@
 // * TwoPassSolve (K <= 4): lmmse_mult(p) for all systems is one A.x and one
 //   A^T.u launch with K right-hand sides per step;
 // * OnePassSolve (K <= 2, the operator planned): A r0 by one A.x pass, then
-//   one pass over X per step (vk::atax); the head start, the pre-step and,
+//   one pass over X per step (vk::atax); the head start, the pre-step (the
+//   slot rule, or two a solve in a third operator slot: DESIGN.md 4.9) and,
 //   on several ranks, the folded decisions live here.
 //
 // The step's scalar decisions run on the device (vk::cg_decide), so the host
@@ -22,6 +23,7 @@
 // The direction update p = z + beta p rides in the next step's kernels.  A
 // step queued after the last system stopped does nothing; its launches are
 // dropped from the stats.
+#include <algorithm>
 #include <cstddef>
 #include <string>
 
@@ -83,8 +85,10 @@ static vampomi_status read_mirror(vampomi_ctx* c, int step, unsigned long long s
 // iteration counts are final).  solve.settle() is called instead of enqueue(i)
 // when no step i is queued (i = max_iter), for a decision of step i-1 that
 // step i's launch would have formed (folded decisions)
+// *nrun (may be null): the steps that ran (every awaited step did)
 template <class Solve>
-static vampomi_status cg_loop(vampomi_ctx* c, int max_iter, bool packed, Solve& solve, CgOutcome* last) {
+static vampomi_status cg_loop(vampomi_ctx* c, int max_iter, bool packed, Solve& solve, CgOutcome* last,
+                              int* nrun = nullptr) {
     unsigned long long prev = 0, cur = 0;
     STCHK(solve.enqueue(0, &prev));
     for (int i = 1;; ++i) {
@@ -98,6 +102,7 @@ static vampomi_status cg_loop(vampomi_ctx* c, int max_iter, bool packed, Solve& 
         STCHK(packed ? read_packed(c, i - 1, prev, last) : read_mirror(c, i - 1, prev, last));
         if (!last->any || i >= max_iter) {
             if (i < max_iter) drop_launches(c, mark, before);  // step i was queued in vain: it did nothing
+            if (nrun) *nrun = i;
             break;
         }
         prev = cur;
@@ -118,6 +123,7 @@ struct Pcg {
     bool head = false;  // the head start (ctx.h, HeadStart) runs
     bool pre_ok = false;  // the pre-step can be made or used: one rank, team plans, packed decisions
     bool pre2 = false;  // system 0's step 1 composed, its step 2 in the head pass
+    int J = 0;          // system 0's composed steps (pre2: 1, or 2 in mode 3); step J + 1 in the head pass
     const double* xnext() const { return a.hs ? a.hs->xnext : nullptr; }
     const int* gate() const { return field<int>(c->cgs, offsetof(vk::CgState, any)); }
     const double* beta() const { return field<double>(c->cgs, offsetof(vk::CgState, beta)); }
@@ -240,6 +246,7 @@ static vampomi_status pcg_start(Pcg& s, bool* go) {
     s.pre_ok = hs && s.op1 && !c->use_comm && c->opp.T >= 1 && hs->T1 && hs->U1 && hs->pre_done && a.max_iter > 0 &&
                a.max_iter < vk::kCgPackMaxIter;
     s.pre2 = s.head && s.pre_ok && hs->pre_have;
+    s.J = !s.pre2 ? 0 : hs->pre3 && hs->n_have >= 2 ? 2 : 1;
     vk::CgVecs cv = fill_vecs(s, false);
     for (int k = 0; k < K; ++k) {
         const CgSystem* y = s.sys[k];
@@ -251,7 +258,7 @@ static vampomi_status pcg_start(Pcg& s, bool* go) {
     s0.gam2 = a.gam2;
     s0.tol = a.tol;
     s0.maxit = a.max_iter;
-    s0.off[0] = s.head ? (s.pre2 ? 2 : 1) : 0;
+    s0.off[0] = s.head ? 1 + s.J : 0;
     s0.any = a.max_iter > 0 ? 1 : 0;
     for (int k = 0; k < K; ++k) {
         s0.active[k] = 1;
@@ -321,6 +328,8 @@ struct OnePassSolve : Pcg {
     const bool packed;
     bool offer = false;  // the pre-step for the next solve: offered to every regular step
     unsigned long long token = 0;
+    bool offer3 = false;  // mode 3: the next solve's two pre-steps in the third slot of steps 0 and 1
+    int nrun = 0;         // the regular steps that ran
 
     explicit OnePassSolve(const Pcg& s)
         : Pcg(s), hs(a.hs), AR(c->op_nvec), Q(AR + (int64_t)vk::kMaxRhs * c->ld),
@@ -383,7 +392,7 @@ struct OnePassSolve : Pcg {
         return ax_products(c, n, pr, given ? a.nscratch : AR);
     }
 
-    // system 0's step 1 (it = -2) from T1, U1 and A r0 = abern: no pass
+    // system 0's step 1 (it = -1 - J) from T1, U1 and A r0 = abern: no pass
     vampomi_status compose_step() {
         vk::PreCompose pc{};
         pc.T1 = hs->T1;
@@ -396,17 +405,57 @@ struct OnePassSolve : Pcg {
         pc.diag = diag;
         pc.tau = a.tau;
         pc.gam2 = a.gam2;
+        if (J == 2) {  // (compose_step2 forms this step's alpha from <r0,z0>)
+            pc.cs = c->cgs;
+            pc.rz_save = hs->rz_save;
+        }
         HIPCHK(vk::pre_compose(c->M, c->N, pc, red(SL_DP, gate()), c->st));
         vk::CgVecs cp = cu;  // A d is the composed vector, whole
         cp.adpart = nullptr;
         cp.addiv = 0.0;
         vk::CgDecide dc{};  // no mirror, no flag: the host does not wait for this step
         dc.on = 1;
-        dc.it = -2;
+        dc.it = -1 - J;
         dc.mask = 1;
         HIPCHK(vk::cg_update(1, c->M, cp, diag, c->cgs, c->scal + SL_DP, nullptr, 0, red(SL_CG, gate()), dc,
                              c->st));
         hs->pre_used = true;
+        hs->n_used = J;
+        return VAMPOMI_OK;
+    }
+
+    // mode 3, two pre-steps in hand: system 0's step 2 (it = -2) from T1, T2,
+    // U1, U2 and the scalars composed step 1 left on the device: no pass.  Its
+    // direction update p1 = z1 + beta0 p0 rides in its cg_update
+    vampomi_status compose_step2() {
+        vk::PreCompose2 pc{};
+        pc.T1 = hs->T1;
+        pc.T2 = hs->T2;
+        pc.U1 = hs->U1;
+        pc.U2 = hs->U2;
+        pc.ar = cu.AR[0];
+        pc.q = cu.Q[0];
+        pc.p = sys[0]->p;
+        pc.z = sys[0]->z;
+        pc.d = sys[0]->d;
+        pc.S = rec ? sys[0]->S : nullptr;
+        pc.AD = const_cast<double*>(cu.AD[0]);
+        pc.diag = diag;
+        pc.tau = a.tau;
+        pc.gam2 = a.gam2;
+        pc.cs = c->cgs;
+        pc.rz_save = hs->rz_save;
+        pc.dp0 = c->scal + SL_DP;
+        HIPCHK(vk::pre_compose2(c->M, c->N, pc, red(SL_DP, gate()), c->st));
+        vk::CgVecs cp = cu;
+        cp.adpart = nullptr;
+        cp.addiv = 0.0;
+        vk::CgDecide dc{};
+        dc.on = 1;
+        dc.it = -2;
+        dc.mask = 1;
+        HIPCHK(vk::cg_update(1, c->M, cp, diag, c->cgs, c->scal + SL_DP, nullptr, 1, red(SL_CG, gate()), dc,
+                             c->st));
         return VAMPOMI_OK;
     }
 
@@ -452,6 +501,13 @@ struct OnePassSolve : Pcg {
         const int fuse = i > 0 ? (1 << K) - 1 : head ? 1 : 0;
         vk::OpArgs o = op_args();
         for (int k = 0; k < K; ++k) op_system(o, k);
+        // mode 3: steps 0 and 1 carry the next solve's pre-steps in a third slot
+        const bool third = offer3 && i < 2;
+        if (third) {
+            o.alt.ar = i == 0 ? hs->axnext : hs->U1;
+            o.alt.p = i == 0 ? hs->xnext : hs->T1;
+            o.alt.d = i == 0 ? hs->T1 : hs->T2;
+        }
         if (offer) {
             o.alt.cs = c->cgs;
             o.alt.done = hs->pre_done;
@@ -477,7 +533,15 @@ struct OnePassSolve : Pcg {
             g = field<int>(cs, offsetof(vk::CgState, any));
             if (!o.fold.on) o.beta = field<double>(cs, offsetof(vk::CgState, beta));
         }
-        STCHK(op_dev(c, K, o, g, c->use_comm, false));
+        STCHK(op_dev(c, third ? vk::kOpSys : K, o, g, c->use_comm, false));
+        vk::CgVecs cv = cu;  // (a 3-system launch left its A d partials in its own plan's slots)
+        if (third) {
+            // U1 / U2: the third slot's team partials in team order, / sqrt(N)
+            vk::Ptrs us{};
+            us.p[0] = i == 0 ? hs->U1 : hs->U2;
+            HIPCHK(vk::op_reduce(c->opp3, 1, c->N, c->ld, c->op_part, us, c->sqrtN, c->st, g, vk::kOpMaxK));
+            cv.adslots = (int)c->opp3.nslots;
+        }
         const double* dp = c->use_comm ? AD + (int64_t)K * c->ld : c->scal + SL_DP;
         *seq = ++c->sync_seq;
         unsigned long long* flag = packed ? c->d_flag + kCgPackWord + (i & 1) : c->d_flag;
@@ -491,7 +555,7 @@ struct OnePassSolve : Pcg {
             dc.seq = *seq;
             dc.pack = packed ? 1 : 0;
         }
-        HIPCHK(vk::cg_update(K, c->M, cu, diag, cs, dp, nullptr, fuse, red(SL_CG, g), dc, c->st));
+        HIPCHK(vk::cg_update(K, c->M, cv, diag, cs, dp, nullptr, fuse, red(SL_CG, g), dc, c->st));
         if (c->use_comm) {
             STCHK(allreduce_dev(c, c->scal + SL_CG, (size_t)(3 * K)));
             if (fold) {  // formed by the next step's operator launch (or settle)
@@ -522,14 +586,22 @@ struct OnePassSolve : Pcg {
         STCHK(op_check_err(c));
         store_iters(*this, last);
         if (offer) hs->pre_made = last.pre;
+        if (offer) hs->n_made = last.pre ? 1 : 0;
+        if (offer3) {  // a step that ran made its pre-step
+            hs->n_made = std::min(nrun, 2);
+            hs->pre_made = hs->n_made > 0;
+        }
         return VAMPOMI_OK;
     }
 
     vampomi_status run() {
         if (!head) STCHK(first_products());
         if (pre2) STCHK(compose_step());
+        if (J == 2) STCHK(compose_step2());
         if (head) STCHK(head_step());
         offer = pre_ok && packed && hs->pre_offer && hs->xnext && hs->axnext && !fold;
+        offer3 = offer && hs->pre3 && c->sys3_ok && hs->T2 && hs->U2;  // (K = 2: pcg_check, the head start's rule)
+        if (offer3) offer = false;  // (no slot rule and no token in mode 3)
         if (offer) {
             token = ++c->pre_seq;
             cu.pre_u1 = hs->U1;
@@ -537,7 +609,7 @@ struct OnePassSolve : Pcg {
             cu.pre_token = token;
         }
         CgOutcome last;
-        STCHK(cg_loop(c, a.max_iter, packed, *this, &last));
+        STCHK(cg_loop(c, a.max_iter, packed, *this, &last, &nrun));
         return finish(last);
     }
 };
@@ -635,7 +707,10 @@ struct TwoPassSolve : Pcg {
 };
 
 vampomi_status pcg_run(vampomi_ctx* c, const std::vector<CgSystem*>& sys, const PcgArgs& args) {
-    if (args.hs) args.hs->used = args.hs->pre_made = args.hs->pre_used = false;
+    if (args.hs) {
+        args.hs->used = args.hs->pre_made = args.hs->pre_used = false;
+        args.hs->n_made = args.hs->n_used = 0;
+    }
     STCHK(pcg_check(c, sys, args));
     bool rec = false;
     for (const CgSystem* y : sys) rec = rec || y->W;

@@ -487,8 +487,55 @@ __global__ __launch_bounds__(kBlock) void pre_compose_kernel(int64_t M, int64_t 
         u += a.gam2 * a.ab[j];
         a.AD[j] = u / a.diag;
     }
+    if (a.rz_save && blockIdx.x == 0 && threadIdx.x == 0) a.rz_save[0] = a.cs->rz[0];
     block_put_sums<1>(acc, 1, ro, (int64_t)blockIdx.x);
     red_finish(ro, 1, lds);
+}
+
+// The second composed step (kernels.h PreCompose2), every expression in the
+// order written there (no contraction).  The sums as pre_compose's
+__global__ __launch_bounds__(kBlock) void pre_compose2_kernel(int64_t M, int64_t N, PreCompose2 a, RedOut ro) {
+    if (ro.gate && !*ro.gate) return;
+    if (!a.cs->active[0]) return;  // the solve stopped inside its composed steps (uniform over the grid)
+    __shared__ double lds[4];
+    const double alpha0 = a.rz_save[0] / a.dp0[0];
+    const double beta0 = a.cs->beta[0];
+    double acc[1] = {0.0};
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < M; i += stride) {
+        const double t1 = a.T1[i];
+        double w = a.tau * a.T2[i];
+        w += a.gam2 * t1;
+        w = w / a.diag;
+        double s = (t1 - alpha0 * w) / a.diag;
+        s = s + beta0 * (t1 / a.diag);
+        const double p1 = a.z[i] + beta0 * a.p[i];
+        double d = s * a.tau;
+        d += a.gam2 * p1;
+        a.d[i] = d;
+        if (a.S) a.S[i] = s;
+        acc[0] += d * p1;
+    }
+    for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < N; j += stride) {
+        const double u1 = a.U1[j];
+        double w = a.tau * a.U2[j];
+        w += a.gam2 * u1;
+        w = w / a.diag;
+        double s = (u1 - alpha0 * w) / a.diag;
+        s = s + beta0 * (u1 / a.diag);
+        double q1 = a.ar[j] / a.diag;
+        q1 = q1 + beta0 * a.q[j];
+        double u = a.tau * s;
+        u += a.gam2 * q1;
+        a.AD[j] = u;
+    }
+    block_put_sums<1>(acc, 1, ro, (int64_t)blockIdx.x);
+    red_finish(ro, 1, lds);
+}
+
+hipError_t pre_compose2(int64_t M, int64_t N, const PreCompose2& a, const RedOut& ro, hipStream_t st) {
+    hipLaunchKernelGGL(pre_compose2_kernel, dim3(red_blocks(M)), dim3(kBlock), 0, st, M, N, a, ro);
+    return hipGetLastError();
 }
 
 hipError_t pre_compose(int64_t M, int64_t N, const PreCompose& a, const RedOut& ro, hipStream_t st) {

@@ -68,6 +68,10 @@ struct VampRun {
     double* pre_t1 = nullptr;
     double* pre_u1 = nullptr;
     int pre_it = 0;
+    // mode 3: T2 = A^T A T1 and U2 = A T2 (+ one scalar, HeadStart.rz_save); pre_n: the pre-steps made for pre_it
+    double* pre_t2 = nullptr;
+    double* pre_u2 = nullptr;
+    int pre_n = 0;
     // the device EM update (vk::EmArgs.upd): the mixture it formed (device
     // words, read by the next denoising) and its mapped host mirror, checked
     // against the host's update (mix_expect) once a later launch has flagged

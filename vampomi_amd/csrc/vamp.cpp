@@ -58,7 +58,7 @@
 VampRun::~VampRun() {
     if (writer) writer->drain(nullptr);  // its kernels read x1 / r1, its thread writes the caller's history arrays
     for (double** p : {&r1, &x1, &x1p, &x1n, &x1d, &r2, &x2, &bern, &invQ, &v, &atxy, &ts, &tmpM, &atx0, &z1buf,
-                       &nb3, &nsc, &ax2, &p1, &p2, &z1h, &x1s, &x1sn, &x2s, &abern, &bern_next, &pre_t1, &pre_u1, &m_cov})
+                       &nb3, &nsc, &ax2, &p1, &p2, &z1h, &x1s, &x1sn, &x2s, &abern, &bern_next, &pre_t1, &pre_u1, &pre_t2, &pre_u2, &m_cov})
         dev_free(*p);
     for (auto& p : cgw) dev_free(p);
     dev_free(mixw);
@@ -529,6 +529,20 @@ static vampomi_status lmmse_setup(vampomi_ctx* c, VampRun& R, int it, const doub
             L.hs.pre_done = reinterpret_cast<unsigned long long*>(R.pre_u1 + ld);
             L.hs.pre_have = L.hs.abern && R.pre_it == it;
             L.hs.pre_offer = L.hs.xnext != nullptr;
+            L.hs.n_have = L.hs.pre_have ? std::max(R.pre_n, 1) : 0;
+            if (prestep_mode(c) == 3) {
+                if (!R.pre_t2) {  // rule 3's second products, and behind U2 the saved <r0,z0>: only where it runs
+                    const size_t Mx = (size_t)std::max<int64_t>(c->M, 1);
+                    STCHK(dev_alloc(&R.pre_t2, Mx));
+                    STCHK(dev_alloc(&R.pre_u2, (size_t)ld + 2));
+                    HIPCHK(hipMemsetAsync(R.pre_t2, 0, Mx * 8, c->st));
+                    HIPCHK(hipMemsetAsync(R.pre_u2, 0, ((size_t)ld + 2) * 8, c->st));
+                }
+                L.hs.pre3 = true;
+                L.hs.T2 = R.pre_t2;
+                L.hs.U2 = R.pre_u2;
+                L.hs.rz_save = R.pre_u2 + ld;
+            }
         }
     }
     // the iteration's elementwise work before the CG solves, in one launch
@@ -669,8 +683,9 @@ static vampomi_status lmmse_solves(vampomi_ctx* c, VampRun& R, int it, LmmseSetu
         R.hs_it = hs.xnext ? it + 1 : 0;
         // T1, U1 made by this solve are the next one's (consumed before that solve refills them)
         R.pre_it = hs.pre_made ? it + 1 : 0;
-        c->pre_made_n += hs.pre_made ? 1 : 0;
-        c->pre_used_n += hs.pre_used ? 1 : 0;
+        R.pre_n = hs.pre_made ? std::max(hs.n_made, 1) : 0;
+        c->pre_made_n += R.pre_n;  // (every pre-step made and every one used: up to two per solve in mode 3)
+        c->pre_used_n += hs.pre_used ? std::max(hs.n_used, 1) : 0;
     } else if (R.fuse) {  // the two solves share each pass
         if (!L.arec) pargs.init = &e1;
         STCHK(pcg_run(c, {&sx, &so}, pargs));
