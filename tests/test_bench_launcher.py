@@ -324,6 +324,10 @@ def test_rehearsal_flow_with_a_stub_library(monkeypatch, capsys):
 
     _stub_library(monkeypatch)
     monkeypatch.setenv("TMPDIR", os.environ.get("TMPDIR", "/tmp"))
+    # rehearse() selects the loopback communicator through the environment of this process: set here, so that it
+    # is put back afterwards and later tests (test_gpu_parity's forced 1-rank RCCL run) do not inherit it
+    monkeypatch.setenv("VAMPOMI_COMM", "loopback")
+    monkeypatch.setenv("VAMPOMI_RUN_ID", os.environ.get("VAMPOMI_RUN_ID", f"rehearse-{os.getpid()}"))
     args = bench.parse_args(["--rehearse", "3", "--rehearse-scale", "0.1", "--steps", "2", "--warmup", "1",
                              "--deadline-s", "120", "--full"])
     try:

@@ -12,7 +12,16 @@ The bars are those of tests/test_gpu_prestep.py (its helpers are used as they
 are): on against off <= 1e-11 per iteration on x1 / r1, params at rtol 1e-11,
 every CG, Onsager and mixture count equal, the oracle's parity at 1e-10; the
 executed passes equal the rule simulated on the run's own counts.
+
+Beside the teams of 2 and 4 the mode runs on every other kind of 3-system
+plan: teams of 8 and of 16, configuration 4 with four loads per lane, and a
+team of 4 beside a main plan that is a team of 2 (tests/test_gpu_sys3.py has
+the single launches of the same plans).  observed, on against off, the worst
+iteration: 4.9e-15 (team of 8, 30 iterations), 1.8e-15 (team of 16), 8.2e-16
+(configuration 4, S = 4), 1.2e-15 (plans of different team size).
 """
+import ctypes as C
+
 import pytest
 
 from test_gpu_prestep import (_assert_bitwise, _assert_close, _assert_parity, _oracle, _problem, _simulate)
@@ -20,11 +29,27 @@ from test_gpu_prestep import (_assert_bitwise, _assert_close, _assert_parity, _o
 va = pytest.importorskip("vampomi_amd")
 
 T2, T4 = 1000 + 2 * 100 + 2, 1000 + 4 * 100 + 4  # operator plans forced through variant 3: teams of 2 and of 4
+# teams of 8 and 16 (the 3-system plan is the same team under configuration 2, one load per lane), a team of 2
+# under configuration 4 at N = 5377 (3-system plan: four loads per lane under configuration 4), and a team of
+# 2 under configuration 5 at N = 7169, beside which the 3-system plan is a team of 4: steps 0 and 1 of every
+# solve launch one plan and later steps the other, in every iteration
+T8, T16, T2C4, T2C5 = 1000 + 8 * 100 + 2, 1000 + 16 * 100 + 2, 1000 + 2 * 100 + 4, 1000 + 2 * 100 + 5
 
 
 def _has_plan3(N, Mt, opv):
     return va.load().vampomi_dev_op3_plan(N, Mt, 256, -1 if opv is None else opv, None, None, None, None, None, None,
                                           None, 0, None) == 0
+
+
+def _plan3(N, Mt, opv):
+    """(T, S, cfg) of the 3-system plan beside variant opv's."""
+    T, S, cfg = (C.c_int() for _ in range(3))
+    assert va.load().vampomi_dev_op3_plan(N, Mt, 256, opv, C.byref(T), C.byref(S), None, None, C.byref(cfg), None,
+                                          None, 0, None) == 0
+    return T.value, S.value, cfg.value
+
+
+PLAN3 = {T8: (8, 1, 2), T16: (16, 1, 2), T2C4: (2, 4, 4), T2C5: (4, 3, 2)}  # at the shapes these variants run at
 
 
 def _simulate3(cg, ons, max_iter):
@@ -118,11 +143,15 @@ def _assert_schedule3(s, max_iter, plan3=True):
 @pytest.mark.parametrize("N,Mt,its,kind,opv", [(3000, 2000, 10, 1, T2), (3000, 2000, 10, 1, T4),
                                                 (4099, 3001, 12, 1, None), (4099, 3001, 12, 1, T2),
                                                 (1000, 2000, 30, 0, None), (1000, 2000, 30, 0, T2),
-                                                (1000, 2000, 30, 0, T4)])
+                                                (1000, 2000, 30, 0, T4), (1000, 2000, 30, 0, T8),
+                                                (2000, 1500, 12, 1, T16), (5377, 1200, 6, 1, T2C4),
+                                                (7169, 1500, 6, 1, T2C5)])
 def test_mode3_against_off_and_the_oracle(N, Mt, its, kind, opv):
     kw = dict(max_iter=its, stop_criteria_thr=0.0)
     plan3 = _has_plan3(N, Mt, opv)
     assert plan3 == (opv is not None)  # (the default plans of these shapes are T = 1)
+    if opv in PLAN3:
+        assert _plan3(N, Mt, opv) == PLAN3[opv]
     a = _run(N, Mt, kind, 3, opv, **kw)
     b = _run(N, Mt, kind, 0, opv, **kw)
     _assert_close(a, b)
@@ -168,15 +197,16 @@ def test_mode3_early_stop():
 
 @pytest.mark.gpu
 def test_mode3_repeatable(monkeypatch):
-    N, Mt = 1000, 2000
-    kw = dict(max_iter=12, stop_criteria_thr=0.0)
-    a = _run(N, Mt, 0, 3, T2, **kw)
-    b = _run(N, Mt, 0, 3, T2, **kw)
-    _assert_bitwise(a, b)
-    monkeypatch.setenv("VAMPOMI_PRE_AHEAD", "0")
-    c = _run(N, Mt, 0, 3, T2, **kw)
-    _assert_bitwise(a, c)
-    assert a["used"] >= 2
+    for N, Mt, kind, opv in ((1000, 2000, 0, T2), (2000, 1500, 1, T16)):
+        kw = dict(max_iter=12, stop_criteria_thr=0.0)
+        monkeypatch.delenv("VAMPOMI_PRE_AHEAD", raising=False)
+        a = _run(N, Mt, kind, 3, opv, **kw)
+        b = _run(N, Mt, kind, 3, opv, **kw)
+        _assert_bitwise(a, b)
+        monkeypatch.setenv("VAMPOMI_PRE_AHEAD", "0")
+        c = _run(N, Mt, kind, 3, opv, **kw)
+        _assert_bitwise(a, c)
+        assert a["used"] >= 2
 
 
 @pytest.mark.gpu
@@ -191,11 +221,14 @@ def test_mode3_without_a_sys3_plan_is_mode1_bitwise():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("storage", ["f32", "u16"])
-def test_mode3_narrow_storage_bitwise_equal_to_fp64_on_the_widened_matrix(storage):
-    N, Mt = 800, 1500  # (the methylation-like design: values in [0, 1], which the 16-bit storage holds)
+@pytest.mark.parametrize("N,Mt,opv,storage", [pytest.param(800, 1500, T2, "f32", id="f32"),
+                                              pytest.param(800, 1500, T2, "u16", id="u16"),
+                                              pytest.param(2000, 1500, T16, "f32", id="2000-1500-2602-f32"),
+                                              pytest.param(2000, 1500, T16, "u16", id="2000-1500-2602-u16")])
+def test_mode3_narrow_storage_bitwise_equal_to_fp64_on_the_widened_matrix(N, Mt, opv, storage):
+    # (the methylation-like design: values in [0, 1], which the 16-bit storage holds)
     kw = dict(max_iter=6, stop_criteria_thr=0.0)
-    a = _run(N, Mt, 1, 3, T2, storage=storage, **kw)
-    b = _run(N, Mt, 1, 3, T2, X=a["stored"], **kw)
+    a = _run(N, Mt, 1, 3, opv, storage=storage, **kw)
+    b = _run(N, Mt, 1, 3, opv, X=a["stored"], **kw)
     _assert_bitwise(a, b)
     assert a["used"] >= 2
